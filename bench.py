@@ -12,14 +12,21 @@ kth-problem-seq.c~:24 and TODO-kth-problem-cgm.c~:48).
 
 Input: counter-based synthetic keys generated on the device (family
 uniform_half = [-2^30, 2^30), the reference's well-defined domain, so the CPU
-baselines are correct runs of the reference).  The answer of every run is
-verified on the device with an exact rank certificate (#<v < k <= #<=v).
+baselines are correct runs of the reference); the same arguments give the
+same keys in every run.  Under --full the answer of every step is verified on
+the device with an exact rank certificate (#<v < k <= #<=v).
 
-Extra fields: "roofline" (streaming kernel k_main: 4 B/key algorithmic bytes /
-its HIP-event-timed duration vs 8 TB/s; traffic from profiles/pmc_traffic.json
-when present) and "cpu_baseline" (rank 0, N = 1: the reference's own seq select
-block, vector.c compiled from /root/reference into oracle/_ref, on a bounded
-sample of the same family).
+A plain run (select workload) sets up, warms up, times the K steps and prints
+the result line.  --dump-outputs DIR also writes what the last timed step
+returned to its caller as DIR/<name>.npy.  --full adds the legs that take runs
+or checks of their own: the exact rank certificate of every answer ("verified",
+which then decides the exit code), "roofline" (streaming kernel k_main: 4 B/key
+algorithmic bytes / its HIP-event-timed duration, from K more steps with events
+on the stream, vs 8 TB/s; traffic from profiles/pmc_traffic.json when present)
+and "cpu_baseline*" (rank 0, N = 1: the reference's own seq select block and
+CGM program, compiled from the reference's sources into oracle/_ref by
+oracle/build_ref.sh, on a bounded sample of the same family and on the GPU's
+own 2^30 keys).
 """
 import argparse
 import ctypes
@@ -61,6 +68,31 @@ def cpu_model():
     except OSError:
         pass
     return platform.processor()
+
+
+DUMP_BUDGET = 60_000_000  # bytes of array data --dump-outputs may write in all (under 64 MB with the .npy headers)
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: {name: tensor} -> DIR/<name>.npy, float32 for float32
+    outputs and float64 for integer ones (int32 and the int64 indices, below
+    2^53, are exact in it).  The arrays share DUMP_BUDGET evenly; one that
+    would take more than its share is written as a fixed sample instead: its
+    flattened elements at sorted positions drawn from a generator seeded by
+    the array's position in the dict, the same in every run."""
+    import numpy as np
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET // max(1, len(arrays))
+    for j, (name, t) in enumerate(arrays.items()):
+        t = torch.as_tensor(t)
+        dt = torch.float32 if t.dtype == torch.float32 else torch.float64
+        cap = share // (4 if dt == torch.float32 else 8)
+        if t.numel() > cap:
+            pick = np.sort(np.random.default_rng(0xD0A7 + j).integers(0, t.numel(), cap))
+            t = t.reshape(-1)[torch.from_numpy(pick).to(t.device)]
+        np.save(os.path.join(dirname, name + ".npy"), t.to(dt).cpu().numpy())
 
 
 RDV_ENV = "KTH_RDV_FILE"  # launch_ranks' file rendezvous (no TCP port to probe and race for)
@@ -365,6 +397,8 @@ def rows_main(args):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     kern_ms = sum(evs[2 * i].elapsed_time(evs[2 * i + 1]) for i in range(args.steps)) / args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"values": vals, "columns": cols_out} if args.topk else {"kth": out})
     # exact check on a slice of rows against torch's sort (total order; no NaNs here)
     chk = min(R, 4096)
     if args.topk:  # same value multiset as torch.topk (order and tie choice differ by contract)
@@ -471,6 +505,8 @@ def topk_main(args):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     call_ms = sum(evs[2 * i].elapsed_time(evs[2 * i + 1]) for i in range(args.steps)) / args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"values": vals, "indices": idx})
     # exact check: same values as torch.topk (smallest), indices point at them, index order
     want = torch.sort(torch.topk(keys, k, largest=False).values).values
     verified = bool(torch.equal(torch.sort(vals).values, want) and torch.equal(keys[idx], vals)
@@ -511,9 +547,15 @@ def main():
     ap.add_argument("--seed", type=lambda s: int(s, 0), default=0x5EED0001)
     ap.add_argument("--k", type=int, default=0, help="global 1-based rank (default n_total/2)")
     ap.add_argument("--cpu-log2n", type=int, default=20, help="CPU baseline size (BASELINE config 1: 2^20)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write the last step's outputs (what its caller receives) as "
+                         "DIR/<name>.npy, float32 / float64, a fixed sample where they exceed 64 MB in all")
+    ap.add_argument("--full", action="store_true",
+                    help="select workload: also certify every answer's rank (\"verified\", the exit code), time K more "
+                         "steps with HIP events (\"roofline\") and run the CPU baselines (\"cpu_baseline*\")")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--no-cpu-full", action="store_true",
-                    help="skip the reference CGM leg at the GPU workload's own size (config 2: 2^30, ~45 s)")
+                    help="--full without the reference CGM leg at the GPU workload's own size (config 2: 2^30, ~45 s)")
     ap.add_argument("--local-shards", type=int, default=1,
                     help="P > 1: P shards of 2^log2n keys on this one GPU through kth_sharded_* (config 3 on one GPU)")
     ap.add_argument("--dist", action="store_true",
@@ -637,49 +679,70 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     barrier()
-    # then the same K steps once more with events around the streaming pass
-    # and each whole select: roofline.avg_launch_ms (not the value)
-    sel.enable_timing(True)
-    torch.cuda.synchronize()
-    barrier()
-    t2 = time.perf_counter()
-    for i in range(args.steps):
-        step(args.warmup + i)
-    torch.cuda.synchronize()
-    elapsed_ev = time.perf_counter() - t2
-    barrier()
-    n_sel, main_ms, total_ms = sel.take_timing()
-    sel.enable_timing(False)
+    answers = local_answers if P > 1 else out.cpu().tolist()
+    v = answers[args.warmup]
+    if args.dump_outputs and rank == 0:  # (every rank holds the same answer)
+        dump_outputs(args.dump_outputs, {"kth": torch.tensor(answers[-1:], dtype=torch.int32)})
+    elapsed_ev = 0.0
+    if args.full:
+        # the same K steps once more with events around the streaming pass
+        # and each whole select: roofline.avg_launch_ms (not the value)
+        sel.enable_timing(True)
+        torch.cuda.synchronize()
+        barrier()
+        t2 = time.perf_counter()
+        for i in range(args.steps):
+            step(args.warmup + i)
+        torch.cuda.synchronize()
+        elapsed_ev = time.perf_counter() - t2
+        barrier()
+        n_sel, main_ms, total_ms = sel.take_timing()
+        sel.enable_timing(False)
     if world > 1:
         t = torch.tensor([elapsed, elapsed_ev], dtype=torch.float64, device=coll_device(dev))
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, elapsed_ev = (float(x) for x in t.tolist())
 
-    # exact rank certificate of every answer (device-side integer counts)
-    answers = local_answers if P > 1 else out.cpu().tolist()
-    v = answers[args.warmup]
-    cnt = torch.zeros(2, dtype=torch.int64, device=dev)
-    for c in torch.split(keys, 1 << 30):  # (bounded temporaries at 2^33)
-        cnt += torch.stack([(c < v).sum(), (c <= v).sum()]).to(torch.int64)
-    if world > 1:
-        cnt = cnt.to(coll_device(dev))
-        dist.all_reduce(cnt)
-    lt, le = (int(x) for x in cnt.tolist())
-    verified = (lt < k <= le) and all(a == v for a in answers)
+    verified = None
+    if args.full:
+        # exact rank certificate of every answer (device-side integer counts)
+        answers = local_answers if P > 1 else out.cpu().tolist()
+        cnt = torch.zeros(2, dtype=torch.int64, device=dev)
+        for c in torch.split(keys, 1 << 30):  # (bounded temporaries at 2^33)
+            cnt += torch.stack([(c < v).sum(), (c <= v).sum()]).to(torch.int64)
+        if world > 1:
+            cnt = cnt.to(coll_device(dev))
+            dist.all_reduce(cnt)
+        lt, le = (int(x) for x in cnt.tolist())
+        verified = (lt < k <= le) and all(a == v for a in answers)
     stats = sel.stats() if not sharded and P == 1 else None
 
     ms_per_step = elapsed * 1e3 / args.steps
     value = n_total / (elapsed / args.steps) / 1e9
-    avg_main_ms = main_ms / max(1, n_sel)
-    achieved = 4.0 * n_local / (avg_main_ms * 1e-3) / 1e9 if avg_main_ms > 0 else None
-    kernel = "kth::k_main (streaming pass)"
-    if P > 1:  # the shards' ctxs are internal to the handle: the whole select, host-timed
-        avg_main_ms = ms_per_step
-        achieved = 4.0 * n_local * P / (ms_per_step * 1e-3) / 1e9
-        kernel = f"whole sharded select ({P} shards on one GPU, host-timed, synchronous)"
-    traffic, traffic_note = pmc_traffic("pmc_traffic.json", args.log2n, args.family)
-    if P > 1:
-        traffic, traffic_note = None, "PMC traffic is measured per k_main launch (one shard), not per sharded select"
+    roofline = None
+    if args.full:
+        avg_main_ms = main_ms / max(1, n_sel)
+        achieved = 4.0 * n_local / (avg_main_ms * 1e-3) / 1e9 if avg_main_ms > 0 else None
+        kernel = "kth::k_main (streaming pass)"
+        if P > 1:  # the shards' ctxs are internal to the handle: the whole select, host-timed
+            avg_main_ms = ms_per_step
+            achieved = 4.0 * n_local * P / (ms_per_step * 1e-3) / 1e9
+            kernel = f"whole sharded select ({P} shards on one GPU, host-timed, synchronous)"
+        traffic, traffic_note = pmc_traffic("pmc_traffic.json", args.log2n, args.family)
+        if P > 1:
+            traffic, traffic_note = None, "PMC traffic is measured per k_main launch (one shard), not per sharded select"
+        roofline = {
+            "bound": "hbm",
+            "kernel": kernel,
+            "achieved": achieved,
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": (achieved / HBM_PEAK_GBS) if achieved else None,
+            "traffic": traffic,
+            "traffic_source": traffic_note,
+            "algorithmic_bytes_per_launch": 4 * n_local * P,
+            "avg_launch_ms": avg_main_ms,
+        }
 
     shared = shared_gpu() and world > 1
     res = {
@@ -708,23 +771,14 @@ def main():
             "ranks": world,
             "rccl_world": None if shared else (comm_world if sharded else None),
         },
-        "roofline": {
-            "bound": "hbm",
-            "kernel": kernel,
-            "achieved": achieved,
-            "peak": HBM_PEAK_GBS,
-            "unit": "GB/s",
-            "frac": (achieved / HBM_PEAK_GBS) if achieved else None,
-            "traffic": traffic,
-            "traffic_source": traffic_note,
-            "algorithmic_bytes_per_launch": 4 * n_local * P,
-            "avg_launch_ms": avg_main_ms,
-        },
-        "verified": bool(verified),
         "answer": v,
-        "whole_select_ms_events": total_ms / max(1, n_sel) if not sharded else None,
-        "ms_per_step_events": elapsed_ev * 1e3 / args.steps,
+        "full": args.full,
     }
+    if args.full:
+        res["roofline"] = roofline
+        res["verified"] = bool(verified)
+        res["whole_select_ms_events"] = total_ms / max(1, n_sel) if not sharded else None
+        res["ms_per_step_events"] = elapsed_ev * 1e3 / args.steps
     if shared:
         res["scaling_point"] = False
         res["note"] = (f"TEST MODE (KTH_SHARE_GPU=1): {world} rank processes share GPU 0 and stage the collectives "
@@ -733,7 +787,7 @@ def main():
         res["path"] = {1: "lds", 2: "radix", 3: "window", 4: "window_fallback"}.get(stats["path"], "?")
         res["candidates"] = stats["candidates"]
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         nc = 1 << args.cpu_log2n
         tmp = torch.empty(nc, dtype=torch.int32, device=dev)
         sel.fill(tmp, nc, family, args.seed, offset=0, n_total=nc)
@@ -768,7 +822,7 @@ def main():
         emit(res)
     if sharded:
         dist.destroy_process_group()
-    return 0 if verified else 1
+    return 0 if verified is not False else 1
 
 
 if __name__ == "__main__":

@@ -224,7 +224,7 @@ def test_bench_two_gpus():
     import sys
     from conftest import REPO
     p = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--log2n", "24", "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline"], cwd=REPO, capture_output=True, text=True, timeout=300)
+                        "--full", "--no-cpu-baseline"], cwd=REPO, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["verified"] is True and line["n_gpus"] == 2 and line["config"]["rccl_world"] == 2, line

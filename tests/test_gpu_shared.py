@@ -41,7 +41,7 @@ def _env(extra):
 
 def test_bench_shared_gpu_two_ranks():
     p = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--log2n", "24", "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline"], cwd=REPO, capture_output=True, text=True, timeout=240,
+                        "--full", "--no-cpu-baseline"], cwd=REPO, capture_output=True, text=True, timeout=240,
                        env=_env({"KTH_SHARE_GPU": "1"}), stdin=subprocess.DEVNULL)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [json.loads(ln) for ln in p.stdout.splitlines() if ln.startswith("{")]

@@ -6,7 +6,7 @@ cd "$GRAFT_REPO_ROOT"; O=gpurun_out/adv; rm -rf $O; mkdir -p $O; export TMPDIR=/
 N=$((1 << 30))
 for fam in uniform_half all_equal few_distinct sorted_asc sorted_desc; do
   for k in 1 $((N / 2)) $N; do
-    timeout -k 10 120 python -u bench.py --family $fam --k $k --steps 20 --warmup 5 --no-cpu-baseline >> $O/adv.jsonl 2>$O/err.log || { echo "$fam k=$k rc=$?"; tail -20 $O/err.log; exit 1; }
+    timeout -k 10 120 python -u bench.py --family $fam --k $k --steps 20 --warmup 5 --full --no-cpu-baseline >> $O/adv.jsonl 2>$O/err.log || { echo "$fam k=$k rc=$?"; tail -20 $O/err.log; exit 1; }
   done
 done
 python3 -c "

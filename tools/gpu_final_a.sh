@@ -9,7 +9,7 @@ echo "== smoke"
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { echo smoke rc=$?; tail -20 $O/smoke.log; exit 1; }
 tail -3 $O/smoke.log
 echo "== bench (driver command)"
-timeout -k 10 600 python -u bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.log 2>&1 || { echo bench rc=$?; tail -20 $O/bench.log; exit 1; }
+timeout -k 10 600 python -u bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench.log 2>&1 || { echo bench rc=$?; tail -20 $O/bench.log; exit 1; }
 tail -1 $O/bench.log | cut -c1-700
 echo "== rocprof (driver command, no CPU baselines)"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/prof.log 2>&1 || { echo prof rc=$?; tail -20 $O/prof.log; exit 1; }
@@ -27,7 +27,7 @@ echo "== config 4 (adversarial families at 2^30)"
 N=$((1 << 30))
 for fam in uniform_half all_equal few_distinct sorted_asc sorted_desc; do
   for k in 1 $((N / 2)) $N; do
-    timeout -k 10 120 python -u bench.py --family $fam --k $k --steps 20 --warmup 5 --no-cpu-baseline >> $O/adv.jsonl 2>$O/adv.err || { echo "$fam k=$k rc=$?"; tail -20 $O/adv.err; exit 1; }
+    timeout -k 10 120 python -u bench.py --family $fam --k $k --steps 20 --warmup 5 --full --no-cpu-baseline >> $O/adv.jsonl 2>$O/adv.err || { echo "$fam k=$k rc=$?"; tail -20 $O/adv.err; exit 1; }
   done
 done
 python3 -c "

@@ -10,7 +10,7 @@ for i in $(seq 1 ${ROUNDS:-3}); do
     lib=mpi-k-selection_amd/lib/variants/libkth_$v.so; e=""
     case $v in base) lib=mpi-k-selection_amd/lib/libkth.so ;; env:*) lib=mpi-k-selection_amd/lib/libkth.so; e=${v#env:} ;; esac
     f=${v//[:=]/_}
-    env $e KTH_LIB=$PWD/$lib timeout -k 10 120 python -u bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline "$@" >> $O/$f.jsonl 2>>$O/$f.err || { echo "$v rc=$?"; tail -20 $O/$f.err; exit 1; }
+    env $e KTH_LIB=$PWD/$lib timeout -k 10 120 python -u bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline "$@" >> $O/$f.jsonl 2>>$O/$f.err || { echo "$v rc=$?"; tail -20 $O/$f.err; exit 1; }
   done
 done
 for v in base $VARIANTS; do
