@@ -10,7 +10,8 @@
  *
  * Conventions (all functions):
  *   - k is 1-based, 1 <= k <= n (as in the reference's VecGet(k-1) call sites).
- *   - Order is signed int32 order (float32: IEEE total order, see rows_f32).
+ *   - Order is signed int32 order (float32: IEEE total order, see "float32
+ *     keys" below).
  *   - The input is NOT modified (the reference sorts in place; both of its
  *     drivers discard the data afterwards, kth-problem-seq.c:36,
  *     TODO-kth-problem-cgm.c:283-284, so not mutating is strictly compatible).
@@ -62,7 +63,8 @@ typedef struct kth_stats {
     uint64_t cnt_eq_lo, cnt_eq_hi;
     uint64_t candidates;   /* keys strictly inside the window                 */
     uint64_t capacity;     /* candidate buffer capacity                       */
-    int32_t answer;
+    int32_t answer;        /* after a float32 select: the answer's bit pattern
+                            * (lo_key / hi_key stay in key space either way)  */
     int32_t error;         /* device-side error word (0 = none)               */
 } kth_stats;
 
@@ -97,6 +99,28 @@ int kth_select_i32_ctx(kth_ctx *ctx, const int32_t *keys, int64_t n, int64_t k, 
  * synchronisation and no allocation once the ctx is reserved for n
  * (graph-capturable). */
 int kth_select_i32_async(kth_ctx *ctx, const int32_t *d_keys, int64_t n, int64_t k, int32_t *d_out);
+
+/* --- float32 keys (one array) ------------------------------------------------
+ * The _f32 twins of the three selects above: same error codes (KTH_EINVAL
+ * before any device work, KTH_ENODEV without a GPU), same stream behaviour,
+ * same cooperative back-off rule, the async form graph-capturable once the ctx
+ * is reserved.  Order, the one kth_select_rows_f32 uses: IEEE total order on
+ * the bit patterns, -0.0 < +0.0, subnormals distinct, every NaN (either sign,
+ * any payload) above +inf and equal to every other NaN.  The returned value
+ * has the bit pattern of an input element, except that a NaN comes back as the
+ * canonical quiet NaN 0x7FC00000.  The input is not modified.
+ * The kernels are the int32 kernels instantiated for float32 words: a word
+ * becomes an ordered int32 right after its load (integer operations only) and
+ * a value turns back into a float only where it leaves the library. */
+int kth_select_f32(const float *keys, int64_t n, int64_t k, float *out); /* host or device keys */
+int kth_select_f32_ctx(kth_ctx *ctx, const float *keys, int64_t n, int64_t k, float *out);
+int kth_select_f32_async(kth_ctx *ctx, const float *d_keys, int64_t n, int64_t k, float *d_out);
+/* The order as numbers: kth_f32_order_key(x) is the uint32 whose unsigned
+ * order is the key order (every NaN -> 0xFFFFFFFF); kth_f32_of_order_key is
+ * its inverse (0xFFFFFFFF -> 0x7FC00000).  Host arithmetic only, no device
+ * needed; the same definition the kernels compile (csrc/kth_device.hpp). */
+uint32_t kth_f32_order_key(float x);
+float kth_f32_of_order_key(uint32_t key);
 
 /* Stats of the last select on this ctx (synchronises the ctx stream). */
 int kth_ctx_last_stats(kth_ctx *ctx, kth_stats *st);
@@ -169,6 +193,14 @@ int kth_topk_rows_f32(kth_ctx *ctx, const float *d_keys, int64_t rows, int32_t c
  * the ctx stream (device memory only); a device-side inconsistency leaves the
  * outputs unwritten and shows as kth_ctx_last_stats().error. */
 int kth_topk_i32(kth_ctx *ctx, const int32_t *d_keys, int64_t n, int64_t k, int largest, int32_t *d_vals,
+                 int64_t *d_idx);
+/* float32 keys, in the order of kth_select_f32 (NaNs last for smallest, first
+ * for largest; a NaN value is written as 0x7FC00000); ties at the k-th key go
+ * to the first ones by index, errors are reported as for kth_topk_i32.  Every
+ * k is exact.  The staged variant of the int32 top-k (n / 65536 < k <= n / 16
+ * on 16-byte aligned keys, which stages the kept keys during the streaming
+ * pass) is int32 only: float32 keys take the row-word path for that k range. */
+int kth_topk_f32(kth_ctx *ctx, const float *d_keys, int64_t n, int64_t k, int largest, float *d_vals,
                  int64_t *d_idx);
 
 /* --- synthetic inputs (bench / tests) --------------------------------------

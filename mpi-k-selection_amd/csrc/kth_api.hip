@@ -91,6 +91,7 @@ constexpr uint64_t DSCAN_PER_WG = 1ull << 16;  // candidates per workgroup of th
 struct kth_ctx {
     int device = 0;
     int main_grid[7] = {0, 0, 0, 0, 0, 0, 0};  // streaming-pass workgroups per k_main<TF> variant (KTH_MAIN_WG_PER_CU overrides)
+    int main_grid_f32[5] = {0, 0, 0, 0, 0};    // ... per k_main<TF, true> (float32 keys; TF 5 / 6 are int32 only)
     bool fault_topk_rank = false;  // KTH_HOOK_FAULT_TOPK_RANK (tests): top-k selects a wrong rank on purpose
     bool fault_barrier = false;    // KTH_HOOK_FAULT_BARRIER (tests): the grid barriers report a timeout
     bool fault_once = false;       // (value 2) only the next cooperative launch does
@@ -137,6 +138,7 @@ struct kth_ctx {
     int32_t *h_status = nullptr;  // pinned
     SelState *h_state = nullptr;  // pinned
     int last_state = -1;
+    bool last_f32 = false;    // the last select's keys were float32 (kth_stats.answer: its bits)
     // timing: event pairs around the streaming pass and around whole selects
     bool timing = false;
     std::vector<hipEvent_t> ev_main, ev_total;
@@ -341,21 +343,25 @@ int level_grid(u64 count, u64 per_wg) {
 
 u64 sparse_wg(const kth_ctx *c) { return c->sparse_per_wg ? c->sparse_per_wg : SPARSE_PER_WG; }
 
+// F32 (here and below): the key kind of a.keys, float32 or int32; the sample
+// and the candidates are order keys either way.
+template <bool F32 = false>
 void launch_level(kth_ctx *c, StepArgs a, bool dense, int grid) {
     if (dense) {
         a.min_per_wg = DENSE_PER_WG;
-        kth::k_level<kth::DENSE_BLK><<<grid, kth::DENSE_BLK, 0, c->stream>>>(a);
+        kth::k_level<kth::DENSE_BLK, F32><<<grid, kth::DENSE_BLK, 0, c->stream>>>(a);
     } else {
         a.min_per_wg = sparse_wg(c);
-        kth::k_level<kth::BLK><<<grid, kth::BLK, 0, c->stream>>>(a);
+        kth::k_level<kth::BLK, F32><<<grid, kth::BLK, 0, c->stream>>>(a);
     }
 }
 
 // ---------------------------------------------------------------- paths
+template <bool F32>
 int run_small(kth_ctx *c, const int32_t *keys, int64_t n, int64_t k, int32_t *d_out, int32_t *d_status) {
     c->last_state = 1;
     ev_main(c);
-    kth::k_small<<<1, kth::SMALL_BLOCK, (size_t)n * 4, c->stream>>>(keys, (u64)n, (u64)k, d_out, d_status,
+    kth::k_small<F32><<<1, kth::SMALL_BLOCK, (size_t)n * 4, c->stream>>>(keys, (u64)n, (u64)k, d_out, d_status,
                                                                     c->st + 1);
     ev_main(c);
     return launch_check();
@@ -386,6 +392,7 @@ uint32_t *pre_set(kth_ctx *c, int set) {
 
 // with_pre: this select's k_main<0> histogrammed the candidates' first digit
 // into PreHist set fin_set
+template <bool F32>
 void launch_finish(kth_ctx *c, StepArgs a, int32_t *d_out, int32_t *d_status, bool with_pre = false) {
     const size_t mine = FSLOT_OFF + (size_t)c->fin_set * FSLOT_WORDS;
     a.stats_zero = c->islots + FSLOT_OFF + (size_t)(1 - c->fin_set) * FSLOT_WORDS;
@@ -395,10 +402,11 @@ void launch_finish(kth_ctx *c, StepArgs a, int32_t *d_out, int32_t *d_status, bo
     x.zero2_words = HSLOT_WORDS;
     x.pre = with_pre ? pre_set(c, c->fin_set) : nullptr;
     x.pre_zero = pre_set(c, 1 - c->fin_set);
-    kth::k_finish<<<c->fin_grid, kth::DENSE_BLK, FIN_DYN_LDS, c->stream>>>(a, x);
+    kth::k_finish<F32><<<c->fin_grid, kth::DENSE_BLK, FIN_DYN_LDS, c->stream>>>(a, x);
     c->fin_set ^= 1;
 }
 
+template <bool F32>
 int run_radix(kth_ctx *c, const int32_t *keys, int64_t n, int64_t k, int32_t *d_out, int32_t *d_status) {
     if (c->coop) {  // three radix levels over the input in one launch
         StepArgs a = step(c, kth::ADV_INIT_FULL, -1, 1, nullptr, nullptr, nullptr);
@@ -407,7 +415,7 @@ int run_radix(kth_ctx *c, const int32_t *keys, int64_t n, int64_t k, int32_t *d_
         a.init_n = (u64)n;
         a.init_k = (u64)k;
         ev_main(c);
-        launch_finish(c, a, d_out, d_status);
+        launch_finish<F32>(c, a, d_out, d_status);
         ev_main(c);
         c->last_state = 1;
         return launch_check();
@@ -418,26 +426,38 @@ int run_radix(kth_ctx *c, const int32_t *keys, int64_t n, int64_t k, int32_t *d_
     a.init_n = (u64)n;
     a.init_k = (u64)k;
     ev_main(c);  // the first radix pass is the dominant kernel here
-    launch_level(c, a, true, level_grid((u64)n, DENSE_PER_WG));
+    launch_level<F32>(c, a, true, level_grid((u64)n, DENSE_PER_WG));
     ev_main(c);
     a = step(c, kth::ADV_PICK, 0, 1, islot(c, 1), islot(c, 2), islot(c, 0));
     a.keys = keys;
     a.n_local = (u64)n;
-    launch_level(c, a, false, level_grid((u64)n, sparse_wg(c)));
+    launch_level<F32>(c, a, false, level_grid((u64)n, sparse_wg(c)));
     a = step(c, kth::ADV_PICK, 1, 0, islot(c, 2), islot(c, 0), islot(c, 1));
     a.keys = keys;
     a.n_local = (u64)n;
-    launch_level(c, a, false, level_grid((u64)n, sparse_wg(c)));
+    launch_level<F32>(c, a, false, level_grid((u64)n, sparse_wg(c)));
     a = step(c, kth::ADV_PICK, 0, 1, islot(c, 0), nullptr, nullptr);
-    kth::k_result<<<1, kth::BLK, 0, c->stream>>>(a, d_out, d_status, c->islots, ISLOT_WORDS);
+    kth::k_result<F32><<<1, kth::BLK, 0, c->stream>>>(a, d_out, d_status, c->islots, ISLOT_WORDS);
     c->last_state = 1;
     return launch_check();
 }
 
 // The streaming pass, plain (tflag 0) or with the top-k records of k_main<tflag>.
+template <bool F32>
 void launch_main(kth_ctx *c, const StepArgs &a, int tflag, uint32_t *tflags) {
-    const int g = c->main_grid[tflag];
     const kth::TkSeg none{};
+    if constexpr (F32) {  // (kth_topk_f32 never asks for the staged variants 5 / 6)
+        const int g = c->main_grid_f32[tflag < 5 ? tflag : 0];
+        switch (tflag) {
+        case 1: kth::k_main<1, true><<<g, kth::BLK, 0, c->stream>>>(a, c->cand, tflags, nullptr, none); break;
+        case 2: kth::k_main<2, true><<<g, kth::BLK, 0, c->stream>>>(a, c->cand, tflags, nullptr, none); break;
+        case 3: kth::k_main<3, true><<<g, kth::BLK, 0, c->stream>>>(a, c->cand, tflags, c->cand_rows, none); break;
+        case 4: kth::k_main<4, true><<<g, kth::BLK, 0, c->stream>>>(a, c->cand, tflags, c->cand_rows, none); break;
+        default: kth::k_main<0, true><<<g, kth::BLK, 0, c->stream>>>(a, c->cand, nullptr, nullptr, none); break;
+        }
+        return;
+    }
+    const int g = c->main_grid[tflag];
     switch (tflag) {
     case 1: kth::k_main<1><<<g, kth::BLK, 0, c->stream>>>(a, c->cand, tflags, nullptr, none); break;
     case 2: kth::k_main<2><<<g, kth::BLK, 0, c->stream>>>(a, c->cand, tflags, nullptr, none); break;
@@ -452,6 +472,7 @@ void launch_main(kth_ctx *c, const StepArgs &a, int tflag, uint32_t *tflags) {
 // The main pass + candidate levels + result, shared by the single-GPU window
 // path.  Expects the window state in st[0] and the last sample digit's
 // histogram in islot(0).
+template <bool F32>
 int run_window(kth_ctx *c, const int32_t *keys, int64_t n, int64_t k, int32_t *d_out, int32_t *d_status,
                int tflag = 0, uint32_t *tflags = nullptr) {
     const int64_t s = sample_size(n);
@@ -481,8 +502,8 @@ int run_window(kth_ctx *c, const int32_t *keys, int64_t n, int64_t k, int32_t *d
         // them, ~1 M candidates, and cost ~10 us more than the level saves)
         kth::CoopArgs hx = coop_args(c, HSLOT_OFF, nullptr, nullptr);
         if (tflag == 0 && c->head_abs_div) hx.abs_min = (u64)s / c->head_abs_div;
-        kth::k_head<<<gather_grid(nchunks), kth::DENSE_BLK, 0, c->stream>>>(a, hx, keys, (u64)n, stride, c->sample,
-                                                                          (u64)s);
+        kth::k_head<F32><<<gather_grid(nchunks), kth::DENSE_BLK, 0, c->stream>>>(a, hx, keys, (u64)n, stride,
+                                                                               c->sample, (u64)s);
         // the streaming pass: counts into islot(1) (zero between selects);
         // the plain pass also histograms the candidates' first digit for k_finish
         a = step(c, kth::ADV_CARRY, 0, 1, nullptr, islot(c, 1), nullptr);
@@ -491,13 +512,13 @@ int run_window(kth_ctx *c, const int32_t *keys, int64_t n, int64_t k, int32_t *d
         const bool pre = tflag == 0 && c->pre_hist;
         if (pre) a.pre_hist = pre_set(c, c->fin_set);
         ev_main(c);
-        launch_main(c, a, tflag, tflags);
+        launch_main<F32>(c, a, tflag, tflags);
         ev_main(c);
         // decide + candidate (or fallback) levels + answer in one launch
         a = step(c, kth::ADV_DECIDE, 1, 0, islot(c, 1), nullptr, nullptr);
         a.keys = keys;
         a.n_local = (u64)n;
-        launch_finish(c, a, d_out, d_status, pre);
+        launch_finish<F32>(c, a, d_out, d_status, pre);
         c->last_state = 0;
         c->counts_left = true;  // (k_head clears them; a sharded select on this ctx must too)
         return launch_check();
@@ -509,8 +530,8 @@ int run_window(kth_ctx *c, const int32_t *keys, int64_t n, int64_t k, int32_t *d
     a.init_s = (u64)s;
     a.r_lo = r_lo;
     a.r_hi = r_hi;
-    kth::k_gather<true><<<gather_grid(nchunks), kth::DENSE_BLK, 0, c->stream>>>(a, keys, (u64)n, stride, c->sample,
-                                                                              (u64)s);
+    kth::k_gather<true, F32><<<gather_grid(nchunks), kth::DENSE_BLK, 0, c->stream>>>(a, keys, (u64)n, stride,
+                                                                                   c->sample, (u64)s);
     // digits 2, 3 of the sample ranks (sparse: only keys in the picked bins)
     const int gs = level_grid((u64)s, sparse_wg(c));
     a = step(c, kth::ADV_PICK, 0, 1, islot(c, 1), islot(c, 2), islot(c, 0));
@@ -526,24 +547,24 @@ int run_window(kth_ctx *c, const int32_t *keys, int64_t n, int64_t k, int32_t *d
     a.keys = keys;
     a.n_local = (u64)n;
     ev_main(c);
-    launch_main(c, a, tflag, tflags);
+    launch_main<F32>(c, a, tflag, tflags);
     ev_main(c);
     // decide + candidate (or fallback) levels.  The grids cover the fallback
     // (whole input); in the common case only the WGs the candidates need run.
     a = step(c, kth::ADV_DECIDE, 1, 0, islot(c, 1), islot(c, 2), islot(c, 0));
     a.keys = keys;
     a.n_local = (u64)n;
-    launch_level(c, a, true, c->post_dense_grid);
+    launch_level<F32>(c, a, true, c->post_dense_grid);
     a = step(c, kth::ADV_PICK, 0, 1, islot(c, 2), islot(c, 0), islot(c, 1));
     a.keys = keys;
     a.n_local = (u64)n;
-    launch_level(c, a, false, c->post_sparse_grid);
+    launch_level<F32>(c, a, false, c->post_sparse_grid);
     a = step(c, kth::ADV_PICK, 1, 0, islot(c, 0), islot(c, 1), islot(c, 2));
     a.keys = keys;
     a.n_local = (u64)n;
-    launch_level(c, a, false, c->post_sparse_grid);
+    launch_level<F32>(c, a, false, c->post_sparse_grid);
     a = step(c, kth::ADV_PICK, 0, 1, islot(c, 1), nullptr, nullptr);
-    kth::k_result<<<1, kth::BLK, 0, c->stream>>>(a, d_out, d_status, c->islots, ISLOT_WORDS);
+    kth::k_result<F32><<<1, kth::BLK, 0, c->stream>>>(a, d_out, d_status, c->islots, ISLOT_WORDS);
     c->last_state = 1;
     return launch_check();
 }
@@ -555,11 +576,13 @@ void coop_tick(kth_ctx *c) {
     if (c->coop_backoff > 0 && --c->coop_backoff == 0) c->coop = c->coop_wanted;
 }
 
+template <bool F32 = false>
 int select_async(kth_ctx *c, const int32_t *d_keys, int64_t n, int64_t k, int32_t *d_out, int32_t *d_status,
                  int tflag = 0, uint32_t *tflags = nullptr) {
     if (!c || !d_keys || (!d_out && !d_status) || n < 1 || k < 1 || k > n) return KTH_EINVAL;
     KTH_TRY(set_device(c));
     coop_tick(c);
+    c->last_f32 = F32;
     if (c->dirty) {
         HIP_TRY(hipMemsetAsync(c->islots, 0, SLOT_ALLOC_WORDS * sizeof(u64), c->stream));
         c->dirty = false;
@@ -567,11 +590,11 @@ int select_async(kth_ctx *c, const int32_t *d_keys, int64_t n, int64_t k, int32_
     int rc;
     ev_mark(c, c->ev_total, c->total_used);
     if (n <= SMALL_N)
-        rc = run_small(c, d_keys, n, k, d_out, d_status);
+        rc = run_small<F32>(c, d_keys, n, k, d_out, d_status);
     else if (n <= RADIX_MAX_N)
-        rc = run_radix(c, d_keys, n, k, d_out, d_status);
+        rc = run_radix<F32>(c, d_keys, n, k, d_out, d_status);
     else
-        rc = run_window(c, d_keys, n, k, d_out, d_status, tflag, tflags);
+        rc = run_window<F32>(c, d_keys, n, k, d_out, d_status, tflag, tflags);
     ev_mark(c, c->ev_total, c->total_used);
     if (rc != KTH_OK) c->dirty = true;
     if (c->stamps) dump_stamps(c);
@@ -702,11 +725,17 @@ int kth_ctx_create(int device, kth_ctx **out) {
                                   reinterpret_cast<const void *>(kth::k_main<4>),
                                   reinterpret_cast<const void *>(kth::k_main<5>),
                                   reinterpret_cast<const void *>(kth::k_main<6>)};
+            // float32 keys: k_main<TF, true>, TF 0..4 (after the int32 ones)
+            const void *fns_f32[5] = {reinterpret_cast<const void *>(kth::k_main<0, true>),
+                                      reinterpret_cast<const void *>(kth::k_main<1, true>),
+                                      reinterpret_cast<const void *>(kth::k_main<2, true>),
+                                      reinterpret_cast<const void *>(kth::k_main<3, true>),
+                                      reinterpret_cast<const void *>(kth::k_main<4, true>)};
             const char *e = getenv("KTH_MAIN_WG_PER_CU");
-            for (int v = 0; v < 7; ++v) {
+            for (int v = 0; v < 12; ++v) {
                 int per = 4;
                 hipFuncAttributes fa;
-                if (hipFuncGetAttributes(&fa, fns[v]) == hipSuccess && fa.numRegs > 0) {
+                if (hipFuncGetAttributes(&fa, v < 7 ? fns[v] : fns_f32[v - 7]) == hipSuccess && fa.numRegs > 0) {
                     const int alloc = (fa.numRegs + 7) / 8 * 8;
                     const int by_vgpr = std::min(8, 512 / alloc);
                     const int lds = (int)fa.sharedSizeBytes;
@@ -715,7 +744,7 @@ int kth_ctx_create(int device, kth_ctx **out) {
                 }
                 (void)hipGetLastError();
                 if (e && atoi(e) > 0) per = atoi(e);
-                c->main_grid[v] = c->num_cu * per;
+                (v < 7 ? c->main_grid[v] : c->main_grid_f32[v - 7]) = c->num_cu * per;
             }
             if (const char *g = getenv("KTH_SPARSE_PER_WG")) c->sparse_per_wg = (u64)std::max(0, atoi(g));
             if (const char *g = getenv("KTH_DSCAN_PER_WG")) c->dscan_per_wg = (u64)std::max(1024, atoi(g));
@@ -747,13 +776,17 @@ int kth_ctx_create(int device, kth_ctx **out) {
             break;
         }
         // dynamic LDS beyond the 64 KiB default for the LDS / rows kernels
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kth::k_small),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kth::k_small<false>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, SMALL_N * 4);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kth::k_small<true>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, SMALL_N * 4);
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kth::k_rows<false>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, KTH_ROWS_MAX_COLS * 4);
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kth::k_rows<true>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, KTH_ROWS_MAX_COLS * 4);
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kth::k_finish),
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kth::k_finish<false>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)FIN_DYN_LDS) != hipSuccess ||
+            hipFuncSetAttribute(reinterpret_cast<const void *>(kth::k_finish<true>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)FIN_DYN_LDS) != hipSuccess)
             c->coop = false;  // no LDS-resident finish: per-level launches
         (void)hipGetLastError();
@@ -771,12 +804,24 @@ int kth_ctx_create(int device, kth_ctx **out) {
         // (kth_select_i32_async, kth_topk_i32, kth_dist_*) report the error in
         // the state (kth_ctx_last_stats) and leave the retry to the caller.
         {
-            int fin_per_cu = 0, head_per_cu = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&fin_per_cu, reinterpret_cast<const void *>(kth::k_finish),
-                                                             kth::DENSE_BLK, FIN_DYN_LDS) != hipSuccess ||
-                hipOccupancyMaxActiveBlocksPerMultiprocessor(&head_per_cu, reinterpret_cast<const void *>(kth::k_head),
-                                                             kth::DENSE_BLK, 0) != hipSuccess)
-                fin_per_cu = head_per_cu = -1;  // query unavailable: trust the static sizing
+            // (both key kinds share the ctx's one coop switch: the smaller of
+            // the int32 and float32 instantiations' figures decides)
+            const void *fin_fns[2] = {reinterpret_cast<const void *>(kth::k_finish<false>),
+                                      reinterpret_cast<const void *>(kth::k_finish<true>)};
+            const void *head_fns[2] = {reinterpret_cast<const void *>(kth::k_head<false>),
+                                       reinterpret_cast<const void *>(kth::k_head<true>)};
+            int fin_per_cu = INT32_MAX, head_per_cu = INT32_MAX;
+            for (int f = 0; f < 2 && fin_per_cu >= 0; ++f) {
+                int fin = 0, head = 0;
+                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&fin, fin_fns[f], kth::DENSE_BLK, FIN_DYN_LDS) !=
+                        hipSuccess ||
+                    hipOccupancyMaxActiveBlocksPerMultiprocessor(&head, head_fns[f], kth::DENSE_BLK, 0) != hipSuccess) {
+                    fin_per_cu = head_per_cu = -1;  // query unavailable: trust the static sizing
+                } else {
+                    fin_per_cu = std::min(fin_per_cu, fin);
+                    head_per_cu = std::min(head_per_cu, head);
+                }
+            }
             (void)hipGetLastError();
             if (fin_per_cu >= 0 &&
                 ((int64_t)fin_per_cu * c->num_cu < c->fin_grid || (int64_t)head_per_cu * c->num_cu < HEAD_GRID_MAX)) {
@@ -877,7 +922,20 @@ int kth_select_i32_async(kth_ctx *c, const int32_t *d_keys, int64_t n, int64_t k
     return select_async(c, d_keys, n, k, d_out, nullptr);
 }
 
-int kth_select_i32_ctx(kth_ctx *c, const int32_t *keys, int64_t n, int64_t k, int32_t *out) {
+int kth_select_f32_async(kth_ctx *c, const float *d_keys, int64_t n, int64_t k, float *d_out) {
+    if (!d_out) return KTH_EINVAL;
+    return select_async<true>(c, reinterpret_cast<const int32_t *>(d_keys), n, k, reinterpret_cast<int32_t *>(d_out),
+                              nullptr);
+}
+
+}  // extern "C"
+
+namespace {
+
+// The synchronous select through a ctx, either key kind (the words travel as
+// int32; *out receives the caller's word: for float32 the answer's bits).
+template <bool F32>
+int select_ctx(kth_ctx *c, const int32_t *keys, int64_t n, int64_t k, int32_t *out) {
     if (!c || !keys || !out || n < 1 || k < 1 || k > n) return KTH_EINVAL;
     KTH_TRY(set_device(c));
     const int32_t *dk = keys;
@@ -886,7 +944,7 @@ int kth_select_i32_ctx(kth_ctx *c, const int32_t *keys, int64_t n, int64_t k, in
         HIP_TRY(hipMemcpyAsync(c->staging, keys, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
         dk = c->staging;
     }
-    KTH_TRY(select_async(c, dk, n, k, nullptr, c->d_status));
+    KTH_TRY(select_async<F32>(c, dk, n, k, nullptr, c->d_status));
     HIP_TRY(hipMemcpyAsync(c->h_status, c->d_status, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (c->h_status[1] == (int32_t)kth::ERR_BARRIER && c->coop) {
@@ -898,7 +956,7 @@ int kth_select_i32_ctx(kth_ctx *c, const int32_t *keys, int64_t n, int64_t k, in
         c->dirty = true;
         c->coop = false;
         c->coop_backoff = COOP_BACKOFF + 1;  // (the retry below counts one)
-        KTH_TRY(select_async(c, dk, n, k, nullptr, c->d_status));
+        KTH_TRY(select_async<F32>(c, dk, n, k, nullptr, c->d_status));
         HIP_TRY(hipMemcpyAsync(c->h_status, c->d_status, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
@@ -906,11 +964,14 @@ int kth_select_i32_ctx(kth_ctx *c, const int32_t *keys, int64_t n, int64_t k, in
         c->dirty = true;
         return KTH_EINTERNAL;
     }
-    *out = c->h_status[0];
+    // d_status[0] is the ordered word (the top-k kernels compare against it);
+    // a float32 answer is its order key turned back into bits
+    *out = F32 ? (int32_t)kth::f32_of_key((uint32_t)c->h_status[0] ^ 0x80000000u) : c->h_status[0];
     return KTH_OK;
 }
 
-int kth_select_i32(const int32_t *keys, int64_t n, int64_t k, int32_t *out) {
+template <bool F32>
+int select_oneshot(const int32_t *keys, int64_t n, int64_t k, int32_t *out) {
     if (!keys || !out || n < 1 || k < 1 || k > n) return KTH_EINVAL;
     if (!tl_ctx) {
         int dev = 0;
@@ -921,7 +982,40 @@ int kth_select_i32(const int32_t *keys, int64_t n, int64_t k, int32_t *out) {
         }
         KTH_TRY(kth_ctx_create(dev, &tl_ctx));
     }
-    return kth_select_i32_ctx(tl_ctx, keys, n, k, out);
+    return select_ctx<F32>(tl_ctx, keys, n, k, out);
+}
+
+}  // namespace
+
+extern "C" {
+
+int kth_select_i32_ctx(kth_ctx *c, const int32_t *keys, int64_t n, int64_t k, int32_t *out) {
+    return select_ctx<false>(c, keys, n, k, out);
+}
+
+int kth_select_f32_ctx(kth_ctx *c, const float *keys, int64_t n, int64_t k, float *out) {
+    return select_ctx<true>(c, reinterpret_cast<const int32_t *>(keys), n, k, reinterpret_cast<int32_t *>(out));
+}
+
+int kth_select_i32(const int32_t *keys, int64_t n, int64_t k, int32_t *out) {
+    return select_oneshot<false>(keys, n, k, out);
+}
+
+int kth_select_f32(const float *keys, int64_t n, int64_t k, float *out) {
+    return select_oneshot<true>(reinterpret_cast<const int32_t *>(keys), n, k, reinterpret_cast<int32_t *>(out));
+}
+
+uint32_t kth_f32_order_key(float x) {
+    uint32_t b;
+    memcpy(&b, &x, sizeof b);
+    return kth::key_of_f32(b);
+}
+
+float kth_f32_of_order_key(uint32_t key) {
+    const uint32_t b = kth::f32_of_key(key);
+    float x;
+    memcpy(&x, &b, sizeof x);
+    return x;
 }
 
 int kth_ctx_coop(const kth_ctx *c) {
@@ -949,7 +1043,7 @@ int kth_ctx_last_stats(kth_ctx *c, kth_stats *out) {
     out->cnt_eq_hi = s.cnt[kth::C_EQHI];
     out->candidates = s.cnt[kth::C_IN];
     out->capacity = c->cand_cap / 4;
-    out->answer = (int32_t)(s.answer ^ 0x80000000u);
+    out->answer = c->last_f32 ? (int32_t)kth::f32_of_key(s.answer) : (int32_t)(s.answer ^ 0x80000000u);
     out->error = (int32_t)s.error;
     return KTH_OK;
 }
@@ -1032,8 +1126,17 @@ int kth_topk_rows_f32(kth_ctx *c, const float *d_keys, int64_t rows, int32_t col
                                    largest ? 0xFFFFFFFFu : 0u, reinterpret_cast<uint32_t *>(d_vals), d_idx);
 }
 
-int kth_topk_i32(kth_ctx *c, const int32_t *d_keys, int64_t n, int64_t k, int largest, int32_t *d_vals,
-                 int64_t *d_idx) {
+}  // extern "C"
+
+namespace {
+
+// Top-k of one array, either key kind.  float32 keys never take the staged
+// variant (k_main<5/6>: its segments hold the caller's words and k_tk5_write
+// copies them out): that k range goes through the row-word path (tf 3 / 4),
+// which is exact for every k.
+template <bool F32>
+int topk_impl(kth_ctx *c, const int32_t *d_keys, int64_t n, int64_t k, int largest, int32_t *d_vals,
+              int64_t *d_idx) {
     if (!c || !d_keys || (!d_vals && !d_idx) || n < 1 || k < 1 || k > n) return KTH_EINVAL;
     KTH_TRY(set_device(c));
     const u64 ntiles = ((u64)n + kth::TK_TILE - 1) / kth::TK_TILE;
@@ -1054,7 +1157,7 @@ int kth_topk_i32(kth_ctx *c, const int32_t *d_keys, int64_t n, int64_t k, int la
     const bool aligned = (reinterpret_cast<uintptr_t>(d_keys) & 15u) == 0;
     const bool window = n > RADIX_MAX_N;
     const bool few = (u64)k * kth::TK_TILE * 64 <= (u64)n;
-    const bool staged = aligned && window && !few && (u64)k * TK_STAGE_MAX_FRAC <= (u64)n && c->topk_stage;
+    const bool staged = !F32 && aligned && window && !few && (u64)k * TK_STAGE_MAX_FRAC <= (u64)n && c->topk_stage;
     const int tf = staged                                  ? (largest ? 6 : 5)
                    : (aligned && window && !few)           ? (largest ? 4 : 3)
                    : (u64)k * kth::TK_TILE <= (u64)n ? (largest ? 2 : 1)
@@ -1063,7 +1166,7 @@ int kth_topk_i32(kth_ctx *c, const int32_t *d_keys, int64_t n, int64_t k, int la
     // tflags: the header and TF 1 / 2's flag bytes after 4 words, TF >= 3's
     // row words after TF_W0 in per-wave segments (kth::rw_index); 256-byte
     // aligned, so that a wave's group of 64 words fills one line
-    const u64 Gm = (u64)c->main_grid[tf];
+    const u64 Gm = (u64)(F32 ? c->main_grid_f32[tf] : c->main_grid[tf]);
     const kth::RowWords rwl{Gm, tf >= 3 ? kth::rw_seg_words(nfull, Gm) : kth::fl_seg_bytes(nfull, Gm)};
     const u64 fwords = tf >= 3 ? kth::TF_W0 + rwl.G * (kth::BLK / kth::WAVE) * rwl.seg
                                : 4 + rwl.G * (kth::BLK / kth::WAVE) * rwl.seg / 4;
@@ -1105,7 +1208,7 @@ int kth_topk_i32(kth_ctx *c, const int32_t *d_keys, int64_t n, int64_t k, int la
     // the k-th smallest (largest: the (n-k+1)-th smallest) -> d_status[0], on the device
     int64_t rank = largest ? n - k + 1 : k;
     if (c->fault_topk_rank && n > 1) rank = rank < n ? rank + 1 : rank - 1;
-    KTH_TRY(select_async(c, d_keys, n, rank, nullptr, c->d_status, tf, tflags));
+    KTH_TRY(select_async<F32>(c, d_keys, n, rank, nullptr, c->d_status, tf, tflags));
     const uint32_t *keys = reinterpret_cast<const uint32_t *>(d_keys);
     const uint32_t flip = largest ? 0xFFFFFFFFu : 0u;
     u64 *toff = c->topk, *bsum = toff + ntiles, *bbase = bsum + 2 * nblk, *meta = bbase + 2 * nblk;
@@ -1125,14 +1228,14 @@ int kth_topk_i32(kth_ctx *c, const int32_t *d_keys, int64_t n, int64_t k, int la
         HIP_TRY(hipMemsetAsync(tcnt, 0, ntiles * 4, c->stream));
         kth::k_topk_cands<<<c->num_cu * 8, kth::TK_BLOCK, 0, c->stream>>>(
             c->cand, c->cand_rows, cand_count(c), c->cand_cap / 4, c->d_status, flip, tcnt, tflags, sel_st);
-        kth::k_topk_count<true, 1><<<g, kth::TK_BLOCK, 0, c->stream>>>(keys, (u64)n, ntiles, c->d_status, flip,
-                                                                          tcnt, tflags, head, nfull, sel_st, ncov, rwl);
+        kth::k_topk_count<true, 1, F32><<<g, kth::TK_BLOCK, 0, c->stream>>>(
+            keys, (u64)n, ntiles, c->d_status, flip, tcnt, tflags, head, nfull, sel_st, ncov, rwl);
     } else if (aligned) {
-        kth::k_topk_count<true, 0><<<g, kth::TK_BLOCK, 0, c->stream>>>(keys, (u64)n, ntiles, c->d_status, flip,
-                                                                           tcnt, tflags, head, nfull, sel_st, 0, rwl);
+        kth::k_topk_count<true, 0, F32><<<g, kth::TK_BLOCK, 0, c->stream>>>(
+            keys, (u64)n, ntiles, c->d_status, flip, tcnt, tflags, head, nfull, sel_st, 0, rwl);
     } else {
-        kth::k_topk_count<false, 0><<<g, kth::TK_BLOCK, 0, c->stream>>>(keys, (u64)n, ntiles, c->d_status, flip,
-                                                                            tcnt, tflags, head, nfull, sel_st, 0, rwl);
+        kth::k_topk_count<false, 0, F32><<<g, kth::TK_BLOCK, 0, c->stream>>>(
+            keys, (u64)n, ntiles, c->d_status, flip, tcnt, tflags, head, nfull, sel_st, 0, rwl);
     }
     // tile offsets, block bases and need in one launch (a bracket failure --
     // counts that do not hold the k-th -- lands in the select's state, where
@@ -1149,12 +1252,26 @@ int kth_topk_i32(kth_ctx *c, const int32_t *d_keys, int64_t n, int64_t k, int la
                                                                           tcnt, toff, bbase, meta, d_vals, d_idx,
                                                                           tflags, ncov);
     } else if (aligned)
-        kth::k_topk_write<true><<<g, kth::TK_BLOCK, 0, c->stream>>>(keys, (u64)n, ntiles, c->d_status, flip, tcnt,
-                                                                    toff, bbase, meta, d_vals, d_idx);
+        kth::k_topk_write<true, false, F32><<<g, kth::TK_BLOCK, 0, c->stream>>>(
+            keys, (u64)n, ntiles, c->d_status, flip, tcnt, toff, bbase, meta, d_vals, d_idx);
     else
-        kth::k_topk_write<false><<<g, kth::TK_BLOCK, 0, c->stream>>>(keys, (u64)n, ntiles, c->d_status, flip, tcnt,
-                                                                     toff, bbase, meta, d_vals, d_idx);
+        kth::k_topk_write<false, false, F32><<<g, kth::TK_BLOCK, 0, c->stream>>>(
+            keys, (u64)n, ntiles, c->d_status, flip, tcnt, toff, bbase, meta, d_vals, d_idx);
     return launch_check();
+}
+
+}  // namespace
+
+extern "C" {
+
+int kth_topk_i32(kth_ctx *c, const int32_t *d_keys, int64_t n, int64_t k, int largest, int32_t *d_vals,
+                 int64_t *d_idx) {
+    return topk_impl<false>(c, d_keys, n, k, largest, d_vals, d_idx);
+}
+
+int kth_topk_f32(kth_ctx *c, const float *d_keys, int64_t n, int64_t k, int largest, float *d_vals, int64_t *d_idx) {
+    return topk_impl<true>(c, reinterpret_cast<const int32_t *>(d_keys), n, k, largest,
+                           reinterpret_cast<int32_t *>(d_vals), d_idx);
 }
 
 int kth_fill_synthetic(kth_ctx *c, int32_t *d_out, int64_t n, int64_t offset, int64_t n_total, int dist, uint64_t seed,
@@ -1260,8 +1377,8 @@ int kth_dist_window(kth_ctx *c, const uint32_t *d_sample, int64_t s_total) {
         kth::CoopArgs x = coop_args(c, HSLOT_OFF, nullptr, nullptr);
         x.sample_ready = 1;
         const int grid = (int)std::min<int64_t>(64, std::max<int64_t>(1, s_total / (16 * 1024)));
-        kth::k_head<<<grid, kth::DENSE_BLK, 0, c->stream>>>(a, x, nullptr, 0, 0, const_cast<uint32_t *>(d_sample),
-                                                           (u64)s_total);
+        kth::k_head<false><<<grid, kth::DENSE_BLK, 0, c->stream>>>(a, x, nullptr, 0, 0,
+                                                                  const_cast<uint32_t *>(d_sample), (u64)s_total);
         c->dist_coop_window = true;
         return launch_check();
     }
@@ -1412,6 +1529,7 @@ static int launch_dresult(kth_ctx *c, int L, int32_t *d_out, uint32_t early) {
     kth::k_dresult<kth::BLK><<<16, kth::BLK, 0, c->stream>>>(a, d_out, c->d_status, c->islots,
                                                             ISLOT_WORDS + HSLOT_WORDS, early);
     c->last_state = 1 - st_in;
+    c->last_f32 = false;  // (the sharded protocol is int32 only)
     return launch_check();
 }
 

@@ -105,6 +105,7 @@ __device__ __forceinline__ uint32_t active_wgs(u64 count, u64 per_wg) {
 // first digit -> up to two more sample digits, each behind a grid barrier.
 // Workgroup 0 publishes the state in a.st_out: MODE_MAIN with the window, or
 // MODE_DONE with an error.  Replaces k_gather<true> + two k_level launches.
+template <bool F32 = false>
 __global__ __launch_bounds__(DENSE_BLK) void k_head(StepArgs a, CoopArgs x, const int32_t *__restrict__ keys,
                                                     u64 n_keys, u64 stride, uint32_t *__restrict__ sample, u64 s) {
     __shared__ SelState ss;
@@ -154,10 +155,10 @@ __global__ __launch_bounds__(DENSE_BLK) void k_head(StepArgs a, CoopArgs x, cons
 #endif
     if (x.sample_ready)
         hist_sample();
-    else if (gather_head_fast<DENSE_BLK, kHeadStore>(keys, stride, sample, s, lh, plan, blockIdx.x, gridDim.x))
+    else if (gather_head_fast<DENSE_BLK, kHeadStore, F32>(keys, stride, sample, s, lh, plan, blockIdx.x, gridDim.x))
         from_chunks = !kHeadStore;
     else
-        gather_chunks<DENSE_BLK, true, true>(keys, n_keys, stride, sample, s, lh, plan);
+        gather_chunks<DENSE_BLK, true, true, F32>(keys, n_keys, stride, sample, s, lh, plan);
 #ifdef KTH_HEAD_DIAG  // diagnostic build: gather / flush / drain times (slots 4-6 are free on an early window)
     KTH_STAMP(a, 4);
 #endif
@@ -184,7 +185,7 @@ __global__ __launch_bounds__(DENSE_BLK) void k_head(StepArgs a, CoopArgs x, cons
         __syncthreads();
         if (from_chunks)  // (the fast gather keeps no sample: writing 4 MiB through and waiting
                           // for it before the barrier cost more than re-reading the chunks)
-            head_hist_chunks<DENSE_BLK>(keys, stride, s, lh, plan, blockIdx.x, gridDim.x);
+            head_hist_chunks<DENSE_BLK, F32>(keys, stride, s, lh, plan, blockIdx.x, gridDim.x);
         else
             hist_sample();
         hist_flush<DENSE_BLK>(lh, plan, x.slots + (size_t)(L + 1) * STATS_WORDS);
@@ -263,6 +264,10 @@ constexpr uint32_t TAIL_STAGE = 2 * NBINS;  // keys a workgroup stages in LDS (t
 // slice lands ~3.5 us after the decide either way; reading and picking
 // PreHist takes ~4 us more, profiles/r5_select_stamps.txt.)
 
+// (a template only so that each k_finish<F32> has its own copy, inlined into
+// its one caller as before: shared between the two kernels it was compiled as
+// a call and k_finish<false> no longer matched the int32-only build)
+template <bool F32>
 __device__ bool finish_tail(const StepArgs &a, SelState &ss, const CoopArgs &x, uint4 *res, u64 nk, bool xr,
                             uint32_t (*lh)[NBINS], u64 *scratch) {
     __shared__ uint32_t s_n, s_last, s_total, s_ln;
@@ -485,6 +490,10 @@ __device__ bool finish_tail(const StepArgs &a, SelState &ss, const CoopArgs &x, 
     return true;
 }
 
+// F32: a.keys holds float32 words.  The input is only read after a window miss
+// or on the radix path (MODE_FULL); its words become ordered words as they are
+// loaded, so the LDS slice, the tail and every later digit see the int32 form.
+template <bool F32 = false>
 __global__ __launch_bounds__(DENSE_BLK) void k_finish(StepArgs a, CoopArgs x) {
     __shared__ SelState ss;
     __shared__ u64 scratch[2 * (DENSE_BLK / WAVE) + 8];
@@ -557,6 +566,8 @@ __global__ __launch_bounds__(DENSE_BLK) void k_finish(StepArgs a, CoopArgs x) {
                             const uint32_t v = v0 + u * DENSE_BLK + threadIdx.x;
                             if (v < nv) {
                                 const u64 e = 4ull * v;
+                                if constexpr (F32)
+                                    if (xr) q[u] = ord_word4<true>(q[u]);
                                 res[v] = q[u];
                                 if (pre0)
                                     ;  // (the digit comes from PreHist)
@@ -575,6 +586,8 @@ __global__ __launch_bounds__(DENSE_BLK) void k_finish(StepArgs a, CoopArgs x) {
                         if (left > 1) q.y = dom[e + 1];
                         if (left > 2) q.z = dom[e + 2];
                         if (left > 3) q.w = dom[e + 3];
+                        if constexpr (F32)
+                            if (xr) q = ord_word4<true>(q);  // (absent keys stay 0: masked off below)
                         res[v] = q;
                         if (!pre0) finish_keys(lh, plan, q, xr, left >= 4 ? 0xFu : (1u << (uint32_t)left) - 1u);
                     }
@@ -595,9 +608,9 @@ __global__ __launch_bounds__(DENSE_BLK) void k_finish(StepArgs a, CoopArgs x) {
             };
             if (blockIdx.x < active) {
                 if (xr)
-                    stream_tiles<DENSE_BLK, FIN_UNROLL, true>(dom, count, blockIdx.x, active, f);
+                    stream_tiles<DENSE_BLK, FIN_UNROLL, F32 ? 2 : 1>(dom, count, blockIdx.x, active, f);
                 else
-                    stream_tiles<DENSE_BLK, FIN_UNROLL, false>(dom, count, blockIdx.x, active, f);
+                    stream_tiles<DENSE_BLK, FIN_UNROLL, 0>(dom, count, blockIdx.x, active, f);
             }
         }
 #ifdef KTH_STAMPS_BUILD  // diagnostic: the slice landed (p2 is free on the PreHist path)
@@ -636,7 +649,7 @@ __global__ __launch_bounds__(DENSE_BLK) void k_finish(StepArgs a, CoopArgs x) {
     grid_bar_finish(gb, s_base);
     bool writer = blockIdx.x == 0;
     if (tail) {
-        writer = finish_tail(a, ss, x, res, nk, xr, lh, scratch);
+        writer = finish_tail<F32>(a, ss, x, res, nk, xr, lh, scratch);
     }
     if (writer && threadIdx.x == 0) {
         SelState o = ss;
@@ -647,7 +660,7 @@ __global__ __launch_bounds__(DENSE_BLK) void k_finish(StepArgs a, CoopArgs x) {
         // only a verified answer reaches d_out: after a barrier timeout (a grid
         // that was not co-resident) or a failed check d_out keeps its value and
         // the error is in the state (kth_ctx_last_stats) and d_status[1]
-        if (x.d_out && !o.error) *x.d_out = i32_of_key(o.answer);
+        if (x.d_out && !o.error) *x.d_out = out_word<F32>(o.answer);
         if (x.d_status) {
             x.d_status[0] = i32_of_key(o.answer);
             x.d_status[1] = (int32_t)o.error;

@@ -68,14 +68,51 @@ struct alignas(16) SelState {
 __device__ __forceinline__ uint32_t key_of_i32(uint32_t bits) { return bits ^ 0x80000000u; }
 __device__ __forceinline__ int32_t i32_of_key(uint32_t key) { return (int32_t)(key ^ 0x80000000u); }
 
-// IEEE-754 total order with every NaN mapped above +inf.
-__device__ __forceinline__ uint32_t key_of_f32(uint32_t b) {
+// IEEE-754 total order with every NaN mapped above +inf.  Host and device
+// share this one definition: kth_f32_order_key / kth_f32_of_order_key
+// (include/kth.h) are these two functions, so a CPU test pins what the
+// kernels compute.
+__host__ __device__ __forceinline__ uint32_t key_of_f32(uint32_t b) {
     if ((b & 0x7FFFFFFFu) > 0x7F800000u) return 0xFFFFFFFFu;
     return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
-__device__ __forceinline__ uint32_t f32_of_key(uint32_t key) {
+__host__ __device__ __forceinline__ uint32_t f32_of_key(uint32_t key) {
     if (key == 0xFFFFFFFFu) return 0x7FC00000u;
     return (key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key;
+}
+
+// Key kinds of the one-array select and top-k.  Their kernels work on
+// "ordered words": int32 words whose signed order is the key order and whose
+// order key is key_of_i32(word).  An int32 input word is one already; a
+// float32 word b becomes one right after its load,
+//   s = (int32)b < 0 ? b ^ 0x7FFFFFFF : b, every NaN -> INT32_MAX,
+// which gives key_of_i32(s) == key_of_f32(b) (negative floats: every bit but
+// the sign flipped, so larger magnitudes order lower).  Integer operations
+// only: float compares or min / max could flush subnormals or quiet NaNs.
+// Everything downstream (window compares, candidates, digits, counts, the
+// top-k's compares) is the int32 code; out_word turns an order key back into
+// the caller's word where a value leaves the library.
+template <bool F32>
+__device__ __forceinline__ uint32_t ord_word(uint32_t b) {
+    if constexpr (F32) {
+        // (a sign test and a select, not a shift and a mask: DESIGN.md,
+        // "float32 keys", Build; worth trying again on a newer toolchain)
+        const uint32_t s = (int32_t)b < 0 ? b ^ 0x7FFFFFFFu : b;
+        return (b & 0x7FFFFFFFu) > 0x7F800000u ? 0x7FFFFFFFu : s;
+    } else {
+        return b;
+    }
+}
+template <bool F32>
+__device__ __forceinline__ uint4 ord_word4(const uint4 &q) {
+    return make_uint4(ord_word<F32>(q.x), ord_word<F32>(q.y), ord_word<F32>(q.z), ord_word<F32>(q.w));
+}
+template <bool F32>
+__device__ __forceinline__ int32_t out_word(uint32_t key) {
+    if constexpr (F32)
+        return (int32_t)f32_of_key(key);
+    else
+        return i32_of_key(key);
 }
 
 __device__ __forceinline__ uint32_t digit_bits(uint32_t W, uint32_t done) {

@@ -328,12 +328,14 @@ __device__ void advance(SelState &ss, const StepArgs &a, u64 *scratch) {
 // (every lane calls f the same number of times; invalid keys are masked off),
 // so f may use ballots and shuffles.  Block-contiguous tiles of BLOCK * UNROLL
 // 16-byte vectors (each wave-instruction reads 1 KiB contiguous), grid-strided;
-// all UNROLL loads of a tile are issued before any is used.  XOR flips the sign
-// bit (int32 -> order-preserving uint32).
-template <int BLOCK, int UNROLL, bool XOR, typename F>
+// all UNROLL loads of a tile are issued before any is used.  KIND: 0 = the words
+// are order keys already; 1 = int32 input (the sign bit is flipped: int32 ->
+// order-preserving uint32); 2 = float32 input (ord_word, then as 1).
+template <int BLOCK, int UNROLL, int KIND, typename F>
 __device__ __forceinline__ void stream_tiles(const uint32_t *__restrict__ p, u64 n, uint32_t wg, uint32_t nwg,
                                              F &&f) {
-    constexpr uint32_t X = XOR ? 0x80000000u : 0u;
+    constexpr uint32_t X = KIND ? 0x80000000u : 0u;
+    constexpr bool F32 = KIND == 2;
     constexpr int K = 4 * UNROLL;
     static_assert(K <= 32, "valid mask is 32 bits");
     const uintptr_t addr = reinterpret_cast<uintptr_t>(p);
@@ -362,10 +364,10 @@ __device__ __forceinline__ void stream_tiles(const uint32_t *__restrict__ p, u64
         }
 #pragma unroll
         for (int u = 0; u < UNROLL; ++u) {
-            k[4 * u + 0] = x[u].x ^ X;
-            k[4 * u + 1] = x[u].y ^ X;
-            k[4 * u + 2] = x[u].z ^ X;
-            k[4 * u + 3] = x[u].w ^ X;
+            k[4 * u + 0] = ord_word<F32>(x[u].x) ^ X;
+            k[4 * u + 1] = ord_word<F32>(x[u].y) ^ X;
+            k[4 * u + 2] = ord_word<F32>(x[u].z) ^ X;
+            k[4 * u + 3] = ord_word<F32>(x[u].w) ^ X;
         }
         if (valid == 0xFFFFFFFFu)
             f(k, valid, std::true_type{});
@@ -377,8 +379,8 @@ __device__ __forceinline__ void stream_tiles(const uint32_t *__restrict__ p, u64
         const bool okh = j < head, okt = j < n - tail0;
 #pragma unroll
         for (int i = 0; i < K; ++i) k[i] = 0;
-        k[0] = (okh ? p[j] : 0u) ^ X;
-        k[1] = (okt ? p[tail0 + j] : 0u) ^ X;
+        k[0] = ord_word<F32>(okh ? p[j] : 0u) ^ X;
+        k[1] = ord_word<F32>(okt ? p[tail0 + j] : 0u) ^ X;
         f(k, (okh ? 1u : 0u) | (okt ? 2u : 0u), std::false_type{});
     }
 }
@@ -446,7 +448,8 @@ __device__ __forceinline__ void publish(const SelState &ss, uint32_t share, cons
 
 // One radix level: advance, then histogram the next digit of every
 // unresolved target over the current domain (sample / candidates / input).
-template <int BLOCK>
+// F32: a.keys holds float32 words (the sample and the candidates are order keys).
+template <int BLOCK, bool F32 = false>
 __global__ __launch_bounds__(BLOCK) void k_level(StepArgs a) {
     __shared__ SelState ss;
     __shared__ u64 scratch[2 * (BLOCK / WAVE) + 8];
@@ -479,11 +482,10 @@ __global__ __launch_bounds__(BLOCK) void k_level(StepArgs a) {
             hist_add<BLOCK>(lh, plan, k[j], decltype(full)::value || ((valid >> j) & 1u));
     };
     if (mode == MODE_FULL)
-        stream_tiles<BLOCK, LEVEL_UNROLL, true>(reinterpret_cast<const uint32_t *>(a.keys), count, blockIdx.x, active,
-                                                f);
+        stream_tiles<BLOCK, LEVEL_UNROLL, F32 ? 2 : 1>(reinterpret_cast<const uint32_t *>(a.keys), count, blockIdx.x,
+                                                       active, f);
     else
-        stream_tiles<BLOCK, LEVEL_UNROLL, false>(mode == MODE_SAMPLE ? a.sample : a.cand, count, blockIdx.x, active,
-                                                 f);
+        stream_tiles<BLOCK, LEVEL_UNROLL, 0>(mode == MODE_SAMPLE ? a.sample : a.cand, count, blockIdx.x, active, f);
     KTH_STAMP(a, 3);
     hist_flush<BLOCK>(lh, plan, a.stats_acc);
     KTH_STAMP(a, 5);
@@ -494,7 +496,7 @@ __global__ __launch_bounds__(BLOCK) void k_level(StepArgs a) {
 // (WAVES per workgroup).  With FUSE the keys also go into the LDS histograms
 // of `plan` (single GPU: the sample is complete).  COHERENT: write-through
 // (sc1) stores, for readers in other workgroups of the same kernel (k_head).
-template <int BLOCK, bool FUSE, bool COHERENT = false>
+template <int BLOCK, bool FUSE, bool COHERENT = false, bool F32 = false>
 __device__ __forceinline__ void gather_chunks(const int32_t *__restrict__ keys, u64 n_keys, u64 stride,
                                               uint32_t *__restrict__ sample, u64 s, uint32_t (*lh)[NBINS],
                                               const HistPlan &plan) {
@@ -521,17 +523,17 @@ __device__ __forceinline__ void gather_chunks(const int32_t *__restrict__ keys, 
 #pragma unroll
                 for (int q = 0; q < NV; ++q) {
                     const uint4 x = src[q * WAVE + lane];
-                    kk[j][4 * q + 0] = key_of_i32(x.x);
-                    kk[j][4 * q + 1] = key_of_i32(x.y);
-                    kk[j][4 * q + 2] = key_of_i32(x.z);
-                    kk[j][4 * q + 3] = key_of_i32(x.w);
+                    kk[j][4 * q + 0] = key_of_i32(ord_word<F32>(x.x));
+                    kk[j][4 * q + 1] = key_of_i32(ord_word<F32>(x.y));
+                    kk[j][4 * q + 2] = key_of_i32(ord_word<F32>(x.z));
+                    kk[j][4 * q + 3] = key_of_i32(ord_word<F32>(x.w));
                 }
             } else {
 #pragma unroll
                 for (int q = 0; q < SAMPLE_CK; ++q) {
                     const u64 off = off_of(q);
                     const bool ok = c < nchunks && c * SAMPLE_CHUNK + off < s && c * stride + off < n_keys;
-                    kk[j][q] = ok ? key_of_i32((uint32_t)keys[c * stride + off]) : 0u;
+                    kk[j][q] = ok ? key_of_i32(ord_word<F32>((uint32_t)keys[c * stride + off])) : 0u;
                 }
             }
         }
@@ -556,7 +558,7 @@ __device__ __forceinline__ void gather_chunks(const int32_t *__restrict__ keys, 
     }
 }
 
-template <bool FUSE>
+template <bool FUSE, bool F32 = false>
 __global__ __launch_bounds__(DENSE_BLK) void k_gather(StepArgs a, const int32_t *__restrict__ keys, u64 n_keys,
                                                 u64 stride, uint32_t *__restrict__ sample, u64 s) {
     __shared__ SelState ss;
@@ -578,6 +580,7 @@ __global__ __launch_bounds__(DENSE_BLK) void k_gather(StepArgs a, const int32_t 
     }
     // (sharded sample, full aligned chunks: a chunk is copied as 16-byte words
     // in the layout gather_chunks writes -- the per-key path took ~8 us)
+    static_assert(FUSE || !F32, "the sharded sample is int32 only");
     const bool vec = !FUSE && s % SAMPLE_CHUNK == 0 && (reinterpret_cast<uintptr_t>(keys) & 15u) == 0 &&
                      stride % 4 == 0 && SAMPLE_CK == 16;
     if (vec) {
@@ -595,7 +598,7 @@ __global__ __launch_bounds__(DENSE_BLK) void k_gather(StepArgs a, const int32_t 
                                                   q[r].w ^ 0x80000000u);
         }
     } else {
-        gather_chunks<DENSE_BLK, FUSE>(keys, n_keys, stride, sample, s, lh, plan);
+        gather_chunks<DENSE_BLK, FUSE, false, F32>(keys, n_keys, stride, sample, s, lh, plan);
     }
     KTH_STAMP(a, 3);
     if (FUSE) hist_flush<DENSE_BLK>(lh, plan, a.stats_acc);
@@ -633,7 +636,7 @@ __device__ __forceinline__ void pick_slot(SelState &ss, const u64 *slot, bool sh
 #define KTH_HEAD_UNI 1
 #endif
 constexpr bool HEAD_UNI = KTH_HEAD_UNI != 0;  // the head's one-bin chunks as one atomic (below)
-template <int BLOCK, bool STORE = true>
+template <int BLOCK, bool STORE = true, bool F32 = false>
 __device__ __forceinline__ bool gather_head_fast(const int32_t *__restrict__ keys, u64 stride, uint32_t *sample,
                                                  u64 s, uint32_t (*lh)[NBINS], const HistPlan &plan,
                                                  uint32_t wg, uint32_t nwg) {
@@ -659,6 +662,7 @@ __device__ __forceinline__ bool gather_head_fast(const int32_t *__restrict__ key
         for (int r = 0; r < 4; ++r) q[r] = src[r * WAVE + lane];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
+            if constexpr (F32) q[r] = ord_word4<true>(q[r]);
             q[r].x ^= 0x80000000u;
             q[r].y ^= 0x80000000u;
             q[r].z ^= 0x80000000u;
@@ -696,7 +700,7 @@ __device__ __forceinline__ bool gather_head_fast(const int32_t *__restrict__ key
 
 // A later sample digit over the full 1024-key chunks of the input themselves
 // (the fast gather keeps no sample): workgroup wg of nwg, plan's histograms.
-template <int BLOCK>
+template <int BLOCK, bool F32 = false>
 __device__ __forceinline__ void head_hist_chunks(const int32_t *__restrict__ keys, u64 stride, u64 s,
                                                  uint32_t (*lh)[NBINS], const HistPlan &plan, uint32_t wg,
                                                  uint32_t nwg) {
@@ -716,6 +720,10 @@ __device__ __forceinline__ void head_hist_chunks(const int32_t *__restrict__ key
         uint4 q[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) q[r] = src[r * WAVE + lane];
+        if constexpr (F32) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) q[r] = ord_word4<true>(q[r]);
+        }
         // the whole chunk in one bin per target (sorted / few-valued input):
         // one atomic per target (as in gather_head_fast)
         const uint32_t f0 = __builtin_amdgcn_readfirstlane(code(q[0].x ^ 0x80000000u, 0)),
@@ -1136,7 +1144,9 @@ __host__ __device__ __forceinline__ u64 rw_index(const RowWords &L, u64 r, uint3
 }
 static_assert(MAIN_UNROLL <= 8, "k_main<TF> keeps one row bit per 16-B load slot in a byte");
 static_assert(BLK / WAVE == 4, "k_main<TF> stores one flag byte per wave, four per tile (tk_row_flagged's mask)");
-template <int TF>
+// F32: a.keys holds float32 words; each loaded tile becomes ordered words
+// (ord_word) before it is scanned, and everything after is the int32 code.
+template <int TF, bool F32 = false>
 __global__ __launch_bounds__(BLK) void k_main(StepArgs a, uint32_t *__restrict__ cand_out,
                                               uint32_t *__restrict__ tflags, uint32_t *__restrict__ cand_rows,
                                               TkSeg seg) {
@@ -1147,6 +1157,7 @@ __global__ __launch_bounds__(BLK) void k_main(StepArgs a, uint32_t *__restrict__
     constexpr bool ROWS = TF == 3 || TF == 4;
 #endif
     constexpr bool ORD = TF >= 5;  // index-ordered staging of the kept side (OrdStager)
+    static_assert(!(F32 && ORD), "the staged top-k is int32 only: its segments hold the caller's words");
     static_assert(U % S == 0, "MAIN_UNROLL is a multiple of MAIN_SUB");
     __shared__ SelState ss;
     __shared__ u64 scratch[2 * (BLK / WAVE) + 8];
@@ -1339,6 +1350,10 @@ __global__ __launch_bounds__(BLK) void k_main(StepArgs a, uint32_t *__restrict__
             load_tile_ord(x, t);
         else
             load_tile(x, t);
+        if constexpr (F32) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) x[u] = ord_word4<true>(x[u]);
+        }
         if constexpr (ORD) {
             // row u: this lane's keys l, 64 + l, 128 + l, 192 + l of the wave's
             // 256 (its wave-row); lane u keeps row u's staged count for the row words
@@ -1419,7 +1434,7 @@ __global__ __launch_bounds__(BLK) void k_main(StepArgs a, uint32_t *__restrict__
             for (int u = 0; u < S; ++u) {
                 const u64 i = rem0 + (h * S + u) * BLK + threadIdx.x;
                 const bool in = i < nv;
-                const uint4 x = in ? v[i] : make_uint4(0, 0, 0, 0);
+                const uint4 x = ord_word4<F32>(in ? v[i] : make_uint4(0, 0, 0, 0));
                 kk[4 * u + 0] = x.x;
                 kk[4 * u + 1] = x.y;
                 kk[4 * u + 2] = x.z;
@@ -1430,7 +1445,8 @@ __global__ __launch_bounds__(BLK) void k_main(StepArgs a, uint32_t *__restrict__
         }
     if (blockIdx.x == 0) {  // the < 4-key unaligned head and tail
         const bool okh = threadIdx.x < head, okt = threadIdx.x < n - tail0;
-        const uint32_t kk[2] = {okh ? p[threadIdx.x] : 0u, okt ? p[tail0 + threadIdx.x] : 0u};
+        const uint32_t kk[2] = {ord_word<F32>(okh ? p[threadIdx.x] : 0u),
+                                ord_word<F32>(okt ? p[tail0 + threadIdx.x] : 0u)};
         scan_keys<2, false>(kk, (okh ? 1u : 0u) | (okt ? 2u : 0u), slo, shi, clt, ceqlo, ceqhi, st);
     }
     // counts: wave reduce -> LDS -> one atomic per workgroup and counter; the
@@ -1515,6 +1531,9 @@ __global__ __launch_bounds__(BLK) void k_main(StepArgs a, uint32_t *__restrict__
 
 // Final digit: one workgroup.  Writes the answer and the error word, then
 // zeroes the ctx-internal slots (and local candidate count) for the next call.
+// d_out takes the caller's word (F32: float bits); d_status[0] stays the
+// ordered word, which the top-k kernels compare against.
+template <bool F32 = false>
 __global__ __launch_bounds__(BLK) void k_result(StepArgs a, int32_t *d_out, int32_t *d_status, u64 *izero,
                                                 u64 izero_words) {
     __shared__ SelState ss;
@@ -1525,7 +1544,7 @@ __global__ __launch_bounds__(BLK) void k_result(StepArgs a, int32_t *d_out, int3
         SelState o = ss;
         if (o.mode != MODE_DONE && !o.error) o.error = 16 + o.mode;
         *a.st_out = o;
-        if (d_out && !o.error) *d_out = i32_of_key(o.answer);  // only a verified answer reaches d_out
+        if (d_out && !o.error) *d_out = out_word<F32>(o.answer);  // only a verified answer reaches d_out
         if (d_status) {
             d_status[0] = i32_of_key(o.answer);
             d_status[1] = (int32_t)o.error;
@@ -1685,7 +1704,7 @@ __device__ __forceinline__ void dist_hist(uint32_t *lh, const uint32_t *dom, u64
                 atomicAdd(&lh[(v >> sh) & mask], 1u);
         }
     };
-    if (blockIdx.x < active) stream_tiles<BLOCK, LEVEL_UNROLL, XOR>(dom, count, blockIdx.x, active, f);
+    if (blockIdx.x < active) stream_tiles<BLOCK, LEVEL_UNROLL, XOR ? 1 : 0>(dom, count, blockIdx.x, active, f);
     __syncthreads();
     for (uint32_t b = threadIdx.x; b <= mask; b += BLOCK) {
         const uint32_t c = lh[b];
@@ -1820,12 +1839,13 @@ __global__ __launch_bounds__(BLOCK) void k_dresult(StepArgs a, int32_t *d_out, i
 }
 
 // n <= 16384: whole selection in one workgroup, keys in LDS.
+template <bool F32 = false>
 __global__ __launch_bounds__(SMALL_BLOCK) void k_small(const int32_t *__restrict__ keys, u64 n, u64 k,
                                                        int32_t *d_out, int32_t *d_status, SelState *st_out) {
     extern __shared__ __attribute__((aligned(16))) uint32_t skeys[];
     __shared__ uint32_t hist[NBINS];
     __shared__ u64 scratch[SMALL_BLOCK / WAVE + 4];
-    for (u64 i = threadIdx.x; i < n; i += SMALL_BLOCK) skeys[i] = key_of_i32((uint32_t)keys[i]);
+    for (u64 i = threadIdx.x; i < n; i += SMALL_BLOCK) skeys[i] = key_of_i32(ord_word<F32>((uint32_t)keys[i]));
     uint32_t prefix = 0, done = 0;
     u64 kk = k;
     bool ok = true;
@@ -1847,7 +1867,7 @@ __global__ __launch_bounds__(SMALL_BLOCK) void k_small(const int32_t *__restrict
         done += d;
     }
     if (threadIdx.x == 0) {
-        if (d_out && ok) d_out[0] = i32_of_key(prefix);
+        if (d_out && ok) d_out[0] = out_word<F32>(prefix);
         if (d_status) {
             d_status[0] = i32_of_key(prefix);
             d_status[1] = ok ? 0 : 1;

@@ -72,7 +72,9 @@ __device__ __forceinline__ bool tk5_ok(const uint32_t *tflags, const int32_t *d_
 }
 
 // MODE: 0 = flags (k_main<1/2>) or none, 1 = row words (k_main<3/4>), 2 = staged (k_main<5/6>)
-template <bool ALIGNED, int MODE>
+// F32: keys holds float32 words (ord_word after each load); d_v, the window
+// in tflags and the candidates are ordered words / order keys either way.
+template <bool ALIGNED, int MODE, bool F32 = false>
 __global__ __launch_bounds__(TK_BLOCK) void k_topk_count(const uint32_t *__restrict__ keys, u64 n, u64 ntiles,
                                                          const int32_t *__restrict__ d_v, uint32_t flip,
                                                          uint32_t *__restrict__ tcnt,
@@ -120,7 +122,7 @@ __global__ __launch_bounds__(TK_BLOCK) void k_topk_count(const uint32_t *__restr
             if (two) todo &= todo - 1;
             uint32_t c1 = 0, c2 = 0;
             auto one = [&](uint32_t &c, uint32_t x) {
-                const uint32_t u = key_of_i32(x);
+                const uint32_t u = key_of_i32(ord_word<F32>(x));
                 c += tk_better(u, uv, flip) ? 1u : 0u;
                 c += u == uv ? 0x10000u : 0u;
             };
@@ -313,7 +315,9 @@ __global__ __launch_bounds__(TK_BLOCK) void k_topk_bases(const uint32_t *__restr
 #define KTH_TKW_TILES 4
 #endif
 constexpr int TKW_TILES = KTH_TKW_TILES;  // tiles a wave loads together in k_topk_write
-template <bool ALIGNED, bool STAGED = false>
+// F32: float32 input; a kept key is written as out_word of its order key (a
+// NaN as the canonical one).
+template <bool ALIGNED, bool STAGED = false, bool F32 = false>
 __global__ __launch_bounds__(TK_BLOCK) void k_topk_write(const uint32_t *__restrict__ keys, u64 n, u64 ntiles,
                                                          const int32_t *__restrict__ d_v, uint32_t flip,
                                                          const uint32_t *__restrict__ tcnt,
@@ -405,7 +409,7 @@ __global__ __launch_bounds__(TK_BLOCK) void k_topk_write(const uint32_t *__restr
 #pragma unroll
                 for (int j = 0; j < TK_KPL; ++j) {
                     const bool in = tb + TK_TILE <= n || tb + (u64)lane * TK_KPL + j < n;
-                    const uint32_t u = key_of_i32(cur.x[q][j]);
+                    const uint32_t u = key_of_i32(ord_word<F32>(cur.x[q][j]));
                     mb |= (uint32_t)(in && tk_better(u, uv, flip)) << j;
                     me |= (uint32_t)(in && u == uv) << j;
                 }
@@ -418,7 +422,10 @@ __global__ __launch_bounds__(TK_BLOCK) void k_topk_write(const uint32_t *__restr
                         const uint32_t isb = (mb >> j) & 1u, ise = (me >> j) & 1u;
                         const uint32_t r = pb + min(pe, cap);
                         if (isb | (ise & (uint32_t)(pe < cap))) {
-                            s_val[w][r] = cur.x[q][j];
+                            if constexpr (F32)
+                                s_val[w][r] = (uint32_t)out_word<true>(key_of_i32(ord_word<true>(cur.x[q][j])));
+                            else
+                                s_val[w][r] = cur.x[q][j];
                             s_col[w][r] = (uint16_t)(lane * TK_KPL + j);
                         }
                         pb += isb;

@@ -8,7 +8,13 @@ Mirrors the reference's selection interface (laertispappas/MPI-k-selection):
     (kth-problem-seq.c:32-33), keeping the VecGet sentinels (-1 NULL, -2 out of
     range, vector.c:209-218).
   * ``kth_select(keys, k)`` / ``Selector`` -- the (data, n, k) -> value contract
-    with explicit errors (``KthError``) instead of in-band sentinels.
+    with explicit errors (``KthError``) instead of in-band sentinels.  Keys are
+    int32 by default; ``f32=True`` on ``kth_select``, ``Selector.select``,
+    ``Selector.select_async`` and ``Selector.topk`` (as on ``rows`` and
+    ``topk_rows``) takes float32 keys in IEEE total order: -0.0 < +0.0,
+    subnormals distinct, every NaN above +inf and returned as 0x7FC00000.
+    Without it a float array is still converted to int32 (numpy) or read as
+    int32 words (tensors), as before.
   * ``kselect.dist`` -- the sharded (one process per GPU) replacement of the CGM
     driver TODO-kth-problem-cgm.c:76-278, with RCCL collectives through
     torch.distributed.
@@ -87,6 +93,18 @@ def _numel(x):
     return x.numel() if hasattr(x, "numel") else len(x)
 
 
+def _need_f32(x, what):
+    """f32=True: anything that carries a dtype (tensor or array) must be float32."""
+    dt = getattr(x, "dtype", None)
+    if dt is not None and str(dt).rsplit(".", 1)[-1] != "float32":
+        raise TypeError(f"{what} must be float32 with f32=True, got {dt}")
+
+
+def _f32_from_bits(bits):
+    """np.float32 holding exactly these 32 bits (signed zeros, subnormals and the NaN kept)."""
+    return np.array([bits & 0xFFFFFFFF], dtype=np.uint32).view(np.float32)[0]
+
+
 def _stream_handle(stream):
     """hipStream_t of a torch stream (0 / None = the null stream, torch's default)."""
     if stream is None:
@@ -140,10 +158,20 @@ class Selector:
         check(LIB.kth_ctx_reserve(self._ctx, int(n)), "kth_ctx_reserve")
 
     # -- selection ---------------------------------------------------------
-    def select(self, keys, k, n=None):
-        """k-th smallest (1-based) of int32 keys (host numpy array or device tensor)."""
+    def select(self, keys, k, n=None, f32=False):
+        """k-th smallest (1-based) of int32 keys (host numpy array or device tensor).
+        f32=True: float32 keys (a host array is taken as np.float32, a tensor must
+        be float32); returns an np.float32 with the answer's exact bits."""
         if n is None:
             n = keys.numel() if hasattr(keys, "numel") else len(keys)
+        if f32:
+            if isinstance(keys, np.ndarray):
+                keys = np.ascontiguousarray(keys, dtype=np.float32)
+            _need_f32(keys, "keys")
+            bits = ctypes.c_uint32()
+            check(LIB.kth_select_f32_ctx(self._ctx, _ptr(keys), int(n), int(k), ctypes.byref(bits)),
+                  "kth_select_f32_ctx")
+            return _f32_from_bits(bits.value)
         if isinstance(keys, np.ndarray):
             keys = np.ascontiguousarray(keys, dtype=np.int32)
         out = ctypes.c_int32()
@@ -151,8 +179,15 @@ class Selector:
               "kth_select_i32_ctx")
         return out.value
 
-    def select_async(self, d_keys, n, k, d_out):
-        """Enqueue a select of device keys; the answer lands in device int32 *d_out."""
+    def select_async(self, d_keys, n, k, d_out, f32=False):
+        """Enqueue a select of device keys; the answer lands in device int32 *d_out
+        (f32=True: float32 keys, float32 *d_out)."""
+        if f32:
+            _need_f32(d_keys, "d_keys")
+            _need_f32(d_out, "d_out")
+            check(LIB.kth_select_f32_async(self._ctx, _ptr(d_keys), int(n), int(k), _ptr(d_out)),
+                  "kth_select_f32_async")
+            return
         check(LIB.kth_select_i32_async(self._ctx, _ptr(d_keys), int(n), int(k), _ptr(d_out)),
               "kth_select_i32_async")
 
@@ -185,13 +220,18 @@ class Selector:
                  _ptr(d_vals) if d_vals is not None else None, _ptr(d_idx) if d_idx is not None else None),
               "kth_topk_rows")
 
-    def topk(self, d_keys, n, k, d_vals=None, d_idx=None, largest=False):
+    def topk(self, d_keys, n, k, d_vals=None, d_idx=None, largest=False, f32=False):
         """The k smallest (largest=True: largest) int32 keys of n device keys and
         their int64 indices, in index order, ties broken by index (kth_topk_i32;
-        asynchronous on the ctx stream)."""
-        check(LIB.kth_topk_i32(self._ctx, _ptr(d_keys), int(n), int(k), 1 if largest else 0,
-                               _ptr(d_vals) if d_vals is not None else None,
-                               _ptr(d_idx) if d_idx is not None else None), "kth_topk_i32")
+        asynchronous on the ctx stream).  f32=True: float32 keys and values
+        (kth_topk_f32; NaNs come first for largest)."""
+        if f32:
+            _need_f32(d_keys, "d_keys")
+            _need_f32(d_vals, "d_vals")
+        fn, what = (LIB.kth_topk_f32, "kth_topk_f32") if f32 else (LIB.kth_topk_i32, "kth_topk_i32")
+        check(fn(self._ctx, _ptr(d_keys), int(n), int(k), 1 if largest else 0,
+                 _ptr(d_vals) if d_vals is not None else None,
+                 _ptr(d_idx) if d_idx is not None else None), what)
 
     def fill(self, d_out, n, family=UNIFORM_FULL, seed=DEFAULT_SEED, param=0, offset=0, n_total=None):
         if isinstance(family, str):
@@ -215,8 +255,17 @@ class Selector:
         return n.value, m.value, t.value
 
 
-def kth_select(keys, k):
-    """One-shot (data, n, k) -> value: kth_select_i32 (kth-problem-seq.c:32-33)."""
+def kth_select(keys, k, f32=False):
+    """One-shot (data, n, k) -> value: kth_select_i32 (kth-problem-seq.c:32-33);
+    f32=True: kth_select_f32 on float32 keys, as Selector.select."""
+    if f32:
+        if isinstance(keys, np.ndarray):
+            keys = np.ascontiguousarray(keys, dtype=np.float32)
+        _need_f32(keys, "keys")
+        n = keys.size if isinstance(keys, np.ndarray) else keys.numel()
+        bits = ctypes.c_uint32()
+        check(LIB.kth_select_f32(_ptr(keys), int(n), int(k), ctypes.byref(bits)), "kth_select_f32")
+        return _f32_from_bits(bits.value)
     if isinstance(keys, np.ndarray):
         keys = np.ascontiguousarray(keys, dtype=np.int32)
         n = keys.size

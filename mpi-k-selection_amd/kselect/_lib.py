@@ -87,6 +87,11 @@ PROTOS = {
     "kth_ctx_reserve": (ctypes.c_int, [c_vp, ctypes.c_int64]),
     "kth_select_i32_ctx": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, c_i32p]),
     "kth_select_i32_async": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, c_vp]),
+    "kth_select_f32": (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int64, c_vp]),
+    "kth_select_f32_ctx": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, c_vp]),
+    "kth_select_f32_async": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, c_vp]),
+    "kth_f32_order_key": (ctypes.c_uint32, [ctypes.c_float]),
+    "kth_f32_of_order_key": (ctypes.c_float, [ctypes.c_uint32]),
     "kth_ctx_last_stats": (ctypes.c_int, [c_vp, ctypes.POINTER(KthStats)]),
     "kth_ctx_coop": (ctypes.c_int, [c_vp]),
     "kth_ctx_test_hook": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int64]),
@@ -100,6 +105,7 @@ PROTOS = {
     "kth_topk_rows_f32": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int,
                                          c_vp, c_vp]),
     "kth_topk_i32": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, c_vp, c_vp]),
+    "kth_topk_f32": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, c_vp, c_vp]),
     "kth_fill_synthetic": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                           ctypes.c_uint64, ctypes.c_int32]),
     "kth_dist_begin": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64]),
