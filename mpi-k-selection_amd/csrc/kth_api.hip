@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -41,7 +42,9 @@ double window_z() {
 }
 constexpr int LEVEL_GRID_MAX = 1024;
 constexpr int POST_DENSE_GRID = 256;  // the candidates need ~100 dense WGs; the rare fallback streams the input with 256
+constexpr int64_t HEAD_PER_WG = 16 * 1024;  // sample keys a k_head workgroup: 16 chunks of 1024
 constexpr int HEAD_GRID_MAX = 64;  // k_head workgroups at most: 2^20 sample keys / (16 chunks of 1024 a workgroup)
+static_assert(HEAD_GRID_MAX == SAMPLE_MAX / HEAD_PER_WG, "k_head's grid covers the largest sample");
 int gather_grid(u64 nchunks) {
     const u64 per_wg = (u64)(kth::DENSE_BLK / kth::WAVE) * kth::GATHER_BATCH;  // chunks per workgroup round
     return (int)std::max<u64>(1, (nchunks + per_wg - 1) / per_wg);
@@ -86,12 +89,44 @@ constexpr uint64_t DSCAN_PER_WG = 1ull << 16;  // candidates per workgroup of th
         if (r_ != KTH_OK) return r_; \
     } while (0)
 
+// A device scratch buffer of a ctx: the pointer and its size in elements.
+template <typename T>
+struct DevBuf {
+    T *p = nullptr;
+    u64 count = 0;
+
+    // At least `want` elements.  Never shrinks; on failure the buffer is empty.
+    int reserve(u64 want) {
+        if (count >= want) return KTH_OK;
+        (void)hipDeviceSynchronize();  // in-flight work may still use the old buffer
+        release();
+        if (hipMalloc(reinterpret_cast<void **>(&p), want * sizeof(T)) != hipSuccess) {
+            (void)hipGetLastError();
+            p = nullptr;
+            return KTH_ENOMEM;
+        }
+        count = want;
+        return KTH_OK;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        count = 0;
+    }
+};
+template <typename... Bufs>
+void release_all(Bufs &...bufs) {
+    (bufs.release(), ...);
+}
+
 }  // namespace
 
 struct kth_ctx {
     int device = 0;
-    int main_grid[7] = {0, 0, 0, 0, 0, 0, 0};  // streaming-pass workgroups per k_main<TF> variant (KTH_MAIN_WG_PER_CU overrides)
-    int main_grid_f32[5] = {0, 0, 0, 0, 0};    // ... per k_main<TF, true> (float32 keys; TF 5 / 6 are int32 only)
+    // streaming-pass workgroups per k_main<TF, F32> variant, [key kind][TF]
+    // (float32 keys have no TF 5 / 6: those entries stay 0)
+    int main_grid[2][7] = {};
+    int main_wg_per_cu = 0;  // KTH_MAIN_WG_PER_CU: k_main workgroups a CU for every variant (0 = from its registers and LDS)
     bool fault_topk_rank = false;  // KTH_HOOK_FAULT_TOPK_RANK (tests): top-k selects a wrong rank on purpose
     bool fault_barrier = false;    // KTH_HOOK_FAULT_BARRIER (tests): the grid barriers report a timeout
     bool fault_once = false;       // (value 2) only the next cooperative launch does
@@ -114,26 +149,17 @@ struct kth_ctx {
     int num_cu = 256;
     SelState *st = nullptr;   // 2 states (ping-pong)
     u64 *islots = nullptr;    // ISLOT_WORDS
-    uint32_t *sample = nullptr;
-    u64 sample_cap = 0;
-    uint32_t *cand = nullptr;
-    u64 cand_cap = 0;
-    uint32_t *cand_rows = nullptr;  // k_main<3/4>: each candidate's 1024-key row (top-k)
-    u64 cand_rows_cap = 0;
+    DevBuf<uint32_t> sample;
+    DevBuf<uint32_t> cand;
+    DevBuf<uint32_t> cand_rows;  // k_main<3/4>: each candidate's 1024-key row (top-k)
     // k_main<5/6> (top-k): per-wave segments of staged keys + positions, per wave-row counts
-    int32_t *tk_segv = nullptr;
-    u64 tk_segv_cap = 0;
-    uint8_t *tk_segp = nullptr;
-    u64 tk_segp_cap = 0;
-    uint32_t *tk_wcnt = nullptr;
-    u64 tk_wcnt_cap = 0;
-    uint32_t *tk_wstart = nullptr;  // staged top-k: entries before each window, per wave
-    u64 tk_wstart_cap = 0;
+    DevBuf<int32_t> tk_segv;
+    DevBuf<uint8_t> tk_segp;
+    DevBuf<uint32_t> tk_wcnt;
+    DevBuf<uint32_t> tk_wstart;  // staged top-k: entries before each window, per wave
     kth::TkSeg tk_seg{};  // the segments of the next launch_main<5/6>
-    int32_t *staging = nullptr;
-    u64 staging_cap = 0;
-    u64 *topk = nullptr;  // top-k chunk counts, bases, [need, error]
-    u64 topk_cap = 0;
+    DevBuf<int32_t> staging;
+    DevBuf<u64> topk;  // top-k chunk counts, bases, [need, error]
     int32_t *d_status = nullptr;  // [answer, error]
     int32_t *h_status = nullptr;  // pinned
     SelState *h_state = nullptr;  // pinned
@@ -167,26 +193,11 @@ struct kth_ctx {
 
 namespace {
 
-u64 *islot(kth_ctx *c, int i) { return c->islots + (size_t)i * kth::STATS_WORDS; }
+// (islot(i) in the comments below: slot i of the three in c->islots)
 u64 *cand_count(kth_ctx *c) { return c->islots + 3 * (size_t)kth::STATS_WORDS; }
 
 int set_device(kth_ctx *c) {
     HIP_TRY(hipSetDevice(c->device));
-    return KTH_OK;
-}
-
-int grow(void **p, u64 *cap, u64 want_bytes) {
-    if (*cap >= want_bytes) return KTH_OK;
-    (void)hipDeviceSynchronize();  // in-flight work may still use the old buffer
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    if (hipMalloc(p, want_bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        *p = nullptr;
-        return KTH_ENOMEM;
-    }
-    *cap = want_bytes;
     return KTH_OK;
 }
 
@@ -197,9 +208,17 @@ int64_t sample_size(int64_t n) {
     return std::min<int64_t>(SAMPLE_MAX, std::max<int64_t>(s, 64));
 }
 
-int reserve_cand(kth_ctx *c, int64_t n) {
-    u64 bytes = cand_capacity(n) * 4;
-    return grow(reinterpret_cast<void **>(&c->cand), &c->cand_cap, bytes);
+// rows: also a row per candidate (k_main<3/4>), as many as there are candidate
+// slots (the kernels bound both by cand.count)
+int reserve_cand(kth_ctx *c, int64_t n, bool rows = false) {
+    KTH_TRY(c->cand.reserve(cand_capacity(n)));
+    return rows ? c->cand_rows.reserve(c->cand.count) : KTH_OK;
+}
+
+// The window path's scratch: the sample and the candidates.
+int reserve_window(kth_ctx *c, int64_t n) {
+    KTH_TRY(c->sample.reserve((u64)sample_size(n)));
+    return reserve_cand(c, n);
 }
 
 // Window ranks in a sample of s keys for rank k of n: +-Z sample sigmas.
@@ -306,10 +325,53 @@ StepArgs step(kth_ctx *c, int adv, int st_in, int st_out, const u64 *in, u64 *ac
     a.stats_acc = acc;
     a.stats_zero = zero;
     a.adv = adv;
-    a.cand = c->cand;
+    a.cand = c->cand.p;
     a.cand_count = cand_count(c);
-    a.cap = c->cand_cap / 4;
+    a.cap = c->cand.count;
     return a;
+}
+
+// A chain of level steps over three rotating histogram slots and the two
+// states.  Step l reads state (l + 1) % 2 and writes state l % 2; it reads slot
+// l % 3, adds into slot (l + 1) % 3 and clears slot (l + 2) % 3 (so every slot
+// is zero again before it is added into).  An ADV_INIT_* step starts a
+// selection and reads no state.  `use` names the slots a step's kernel gets
+// (the others are nullptr): the first step has no histogram to read, a result
+// step adds and clears nothing, and a cooperative kernel that stands for
+// several steps takes the position of its last one.
+struct Chain {
+    enum : unsigned { NONE = 0, IN = 1, ACC = 2, ZERO = 4, ALL = IN | ACC | ZERO };
+    kth_ctx *c;
+    u64 *slots;  // the three slots: c->islots, or the sharded protocol's c->uslots
+    int l = 0;   // the next step
+
+    u64 *slot(int i) const { return slots + (size_t)(i % 3) * kth::STATS_WORDS; }
+    StepArgs next(int adv, unsigned use = ALL) {
+        const bool init = adv == kth::ADV_INIT_SAMPLE || adv == kth::ADV_INIT_FULL;
+        StepArgs a = step(c, adv, init ? -1 : (l + 1) % 2, l % 2, use & IN ? slot(l) : nullptr,
+                          use & ACC ? slot(l + 1) : nullptr, use & ZERO ? slot(l + 2) : nullptr);
+        ++l;
+        return a;
+    }
+};
+
+// StepArgs: the level runs over these input keys / over this sample (order keys)
+void over_keys(StepArgs &a, const int32_t *keys, int64_t n) {
+    a.keys = keys;
+    a.n_local = (u64)n;
+}
+void over_sample(StepArgs &a, const uint32_t *sample, int64_t s) {
+    a.sample = sample;
+    a.sample_count = (u64)s;
+}
+// ... an ADV_INIT_* step's rank k of n and, for a window select, the window's
+// ranks in the sample of s keys
+void init_rank(StepArgs &a, int64_t n, int64_t k, int64_t s = 0, u64 r_lo = 0, u64 r_hi = 0) {
+    a.init_n = (u64)n;
+    a.init_k = (u64)k;
+    a.init_s = (u64)s;
+    a.r_lo = r_lo;
+    a.r_hi = r_hi;
 }
 
 // Record one event of a (start, end) pair; pairs are never split because the
@@ -408,64 +470,67 @@ void launch_finish(kth_ctx *c, StepArgs a, int32_t *d_out, int32_t *d_status, bo
 
 template <bool F32>
 int run_radix(kth_ctx *c, const int32_t *keys, int64_t n, int64_t k, int32_t *d_out, int32_t *d_status) {
-    if (c->coop) {  // three radix levels over the input in one launch
-        StepArgs a = step(c, kth::ADV_INIT_FULL, -1, 1, nullptr, nullptr, nullptr);
-        a.keys = keys;
-        a.n_local = (u64)n;
-        a.init_n = (u64)n;
-        a.init_k = (u64)k;
+    if (c->coop) {  // three radix levels over the input in one launch (steps 0 to 3: the state ends in st[1])
+        StepArgs a = Chain{c, c->islots, 3}.next(kth::ADV_INIT_FULL, Chain::NONE);
+        over_keys(a, keys, n);
+        init_rank(a, n, k);
         ev_main(c);
         launch_finish<F32>(c, a, d_out, d_status);
         ev_main(c);
         c->last_state = 1;
         return launch_check();
     }
-    StepArgs a = step(c, kth::ADV_INIT_FULL, -1, 0, nullptr, islot(c, 1), islot(c, 2));
-    a.keys = keys;
-    a.n_local = (u64)n;
-    a.init_n = (u64)n;
-    a.init_k = (u64)k;
+    Chain ch{c, c->islots};
+    StepArgs a = ch.next(kth::ADV_INIT_FULL, Chain::ACC | Chain::ZERO);
+    over_keys(a, keys, n);
+    init_rank(a, n, k);
     ev_main(c);  // the first radix pass is the dominant kernel here
     launch_level<F32>(c, a, true, level_grid((u64)n, DENSE_PER_WG));
     ev_main(c);
-    a = step(c, kth::ADV_PICK, 0, 1, islot(c, 1), islot(c, 2), islot(c, 0));
-    a.keys = keys;
-    a.n_local = (u64)n;
-    launch_level<F32>(c, a, false, level_grid((u64)n, sparse_wg(c)));
-    a = step(c, kth::ADV_PICK, 1, 0, islot(c, 2), islot(c, 0), islot(c, 1));
-    a.keys = keys;
-    a.n_local = (u64)n;
-    launch_level<F32>(c, a, false, level_grid((u64)n, sparse_wg(c)));
-    a = step(c, kth::ADV_PICK, 0, 1, islot(c, 0), nullptr, nullptr);
+    for (int digit = 1; digit <= 2; ++digit) {
+        a = ch.next(kth::ADV_PICK);
+        over_keys(a, keys, n);
+        launch_level<F32>(c, a, false, level_grid((u64)n, sparse_wg(c)));
+    }
+    a = ch.next(kth::ADV_PICK, Chain::IN);
     kth::k_result<F32><<<1, kth::BLK, 0, c->stream>>>(a, d_out, d_status, c->islots, ISLOT_WORDS);
     c->last_state = 1;
     return launch_check();
+}
+
+// k_head's step: the sample phase of a window select in one launch, so `ch`
+// stands at step 2 (k_head is steps 0 to 2), the window state left in st[0].
+// clear_counts: it also clears the streaming pass's count slot islot(1),
+// islot(2) and the candidate count, which the cooperative single-GPU select
+// leaves behind.
+StepArgs head_step(Chain &ch, int64_t n, int64_t k, int64_t s, u64 r_lo, u64 r_hi, bool clear_counts) {
+    StepArgs a = ch.next(kth::ADV_INIT_SAMPLE, clear_counts ? Chain::ZERO : Chain::NONE);
+    if (clear_counts) a.zero_words = 2 * (u64)kth::STATS_WORDS + 1;
+    init_rank(a, n, k, s, r_lo, r_hi);
+    return a;
 }
 
 // The streaming pass, plain (tflag 0) or with the top-k records of k_main<tflag>.
 template <bool F32>
 void launch_main(kth_ctx *c, const StepArgs &a, int tflag, uint32_t *tflags) {
     const kth::TkSeg none{};
-    if constexpr (F32) {  // (kth_topk_f32 never asks for the staged variants 5 / 6)
-        const int g = c->main_grid_f32[tflag < 5 ? tflag : 0];
-        switch (tflag) {
-        case 1: kth::k_main<1, true><<<g, kth::BLK, 0, c->stream>>>(a, c->cand, tflags, nullptr, none); break;
-        case 2: kth::k_main<2, true><<<g, kth::BLK, 0, c->stream>>>(a, c->cand, tflags, nullptr, none); break;
-        case 3: kth::k_main<3, true><<<g, kth::BLK, 0, c->stream>>>(a, c->cand, tflags, c->cand_rows, none); break;
-        case 4: kth::k_main<4, true><<<g, kth::BLK, 0, c->stream>>>(a, c->cand, tflags, c->cand_rows, none); break;
-        default: kth::k_main<0, true><<<g, kth::BLK, 0, c->stream>>>(a, c->cand, nullptr, nullptr, none); break;
-        }
-        return;
-    }
-    const int g = c->main_grid[tflag];
+    // (the staged variants 5 / 6 exist for int32 keys only, and kth_topk_f32
+    // never asks for them; a float32 pass that did would run plain)
+    if (F32 && tflag >= 5) tflag = 0;
+    const int g = c->main_grid[F32][tflag];
+    uint32_t *cand = c->cand.p, *rows = c->cand_rows.p;
     switch (tflag) {
-    case 1: kth::k_main<1><<<g, kth::BLK, 0, c->stream>>>(a, c->cand, tflags, nullptr, none); break;
-    case 2: kth::k_main<2><<<g, kth::BLK, 0, c->stream>>>(a, c->cand, tflags, nullptr, none); break;
-    case 3: kth::k_main<3><<<g, kth::BLK, 0, c->stream>>>(a, c->cand, tflags, c->cand_rows, none); break;
-    case 4: kth::k_main<4><<<g, kth::BLK, 0, c->stream>>>(a, c->cand, tflags, c->cand_rows, none); break;
-    case 5: kth::k_main<5><<<g, kth::BLK, 0, c->stream>>>(a, c->cand, tflags, nullptr, c->tk_seg); break;
-    case 6: kth::k_main<6><<<g, kth::BLK, 0, c->stream>>>(a, c->cand, tflags, nullptr, c->tk_seg); break;
-    default: kth::k_main<0><<<g, kth::BLK, 0, c->stream>>>(a, c->cand, nullptr, nullptr, none); break;
+    case 1: kth::k_main<1, F32><<<g, kth::BLK, 0, c->stream>>>(a, cand, tflags, nullptr, none); break;
+    case 2: kth::k_main<2, F32><<<g, kth::BLK, 0, c->stream>>>(a, cand, tflags, nullptr, none); break;
+    case 3: kth::k_main<3, F32><<<g, kth::BLK, 0, c->stream>>>(a, cand, tflags, rows, none); break;
+    case 4: kth::k_main<4, F32><<<g, kth::BLK, 0, c->stream>>>(a, cand, tflags, rows, none); break;
+    case 5:
+        if constexpr (!F32) kth::k_main<5><<<g, kth::BLK, 0, c->stream>>>(a, cand, tflags, nullptr, c->tk_seg);
+        break;
+    case 6:
+        if constexpr (!F32) kth::k_main<6><<<g, kth::BLK, 0, c->stream>>>(a, cand, tflags, nullptr, c->tk_seg);
+        break;
+    default: kth::k_main<0, F32><<<g, kth::BLK, 0, c->stream>>>(a, cand, nullptr, nullptr, none); break;
     }
 }
 
@@ -480,19 +545,13 @@ int run_window(kth_ctx *c, const int32_t *keys, int64_t n, int64_t k, int32_t *d
     const u64 stride = (u64)n / nchunks;
     u64 r_lo, r_hi;
     window_ranks(n, k, s, &r_lo, &r_hi);
-    KTH_TRY(grow(reinterpret_cast<void **>(&c->sample), &c->sample_cap, (u64)s * 4));
-    KTH_TRY(reserve_cand(c, n));
+    KTH_TRY(reserve_window(c, n));
 
     if (c->coop) {
         // sample phase in one launch -> window state in st[0]
         // (it also clears the streaming pass's count slot islot(1) and the candidate count)
-        StepArgs a = step(c, kth::ADV_INIT_SAMPLE, -1, 0, nullptr, nullptr, islot(c, 1));
-        a.zero_words = 2 * (u64)kth::STATS_WORDS + 1;
-        a.init_n = (u64)n;
-        a.init_k = (u64)k;
-        a.init_s = (u64)s;
-        a.r_lo = r_lo;
-        a.r_hi = r_hi;
+        Chain ch{c, c->islots, 2};
+        StepArgs a = head_step(ch, n, k, s, r_lo, r_hi, true);
         // the plain select takes a first-level window of up to s / head_abs_div
         // sample keys (~n / 1024 candidates) whatever the slack: at k near 1 or
         // n it spares the second sample level (the top-k variants keep the
@@ -503,68 +562,63 @@ int run_window(kth_ctx *c, const int32_t *keys, int64_t n, int64_t k, int32_t *d
         kth::CoopArgs hx = coop_args(c, HSLOT_OFF, nullptr, nullptr);
         if (tflag == 0 && c->head_abs_div) hx.abs_min = (u64)s / c->head_abs_div;
         kth::k_head<F32><<<gather_grid(nchunks), kth::DENSE_BLK, 0, c->stream>>>(a, hx, keys, (u64)n, stride,
-                                                                               c->sample, (u64)s);
+                                                                               c->sample.p, (u64)s);
         // the streaming pass: counts into islot(1) (zero between selects);
         // the plain pass also histograms the candidates' first digit for k_finish
-        a = step(c, kth::ADV_CARRY, 0, 1, nullptr, islot(c, 1), nullptr);
-        a.keys = keys;
-        a.n_local = (u64)n;
+        a = ch.next(kth::ADV_CARRY, Chain::ACC);
+        over_keys(a, keys, n);
         const bool pre = tflag == 0 && c->pre_hist;
         if (pre) a.pre_hist = pre_set(c, c->fin_set);
         ev_main(c);
         launch_main<F32>(c, a, tflag, tflags);
         ev_main(c);
         // decide + candidate (or fallback) levels + answer in one launch
-        a = step(c, kth::ADV_DECIDE, 1, 0, islot(c, 1), nullptr, nullptr);
-        a.keys = keys;
-        a.n_local = (u64)n;
+        a = ch.next(kth::ADV_DECIDE, Chain::IN);
+        over_keys(a, keys, n);
         launch_finish<F32>(c, a, d_out, d_status, pre);
         c->last_state = 0;
         c->counts_left = true;  // (k_head clears them; a sharded select on this ctx must too)
         return launch_check();
     }
     // sample + first digit of the sample
-    StepArgs a = step(c, kth::ADV_INIT_SAMPLE, -1, 0, nullptr, islot(c, 1), islot(c, 2));
-    a.init_n = (u64)n;
-    a.init_k = (u64)k;
-    a.init_s = (u64)s;
-    a.r_lo = r_lo;
-    a.r_hi = r_hi;
+    Chain ch{c, c->islots};
+    StepArgs a = ch.next(kth::ADV_INIT_SAMPLE, Chain::ACC | Chain::ZERO);
+    init_rank(a, n, k, s, r_lo, r_hi);
     kth::k_gather<true, F32><<<gather_grid(nchunks), kth::DENSE_BLK, 0, c->stream>>>(a, keys, (u64)n, stride,
-                                                                                   c->sample, (u64)s);
+                                                                                   c->sample.p, (u64)s);
     // digits 2, 3 of the sample ranks (sparse: only keys in the picked bins)
     const int gs = level_grid((u64)s, sparse_wg(c));
-    a = step(c, kth::ADV_PICK, 0, 1, islot(c, 1), islot(c, 2), islot(c, 0));
-    a.sample = c->sample;
-    a.sample_count = (u64)s;
-    launch_level(c, a, false, gs);
-    a = step(c, kth::ADV_PICK, 1, 0, islot(c, 2), islot(c, 0), islot(c, 1));
-    a.sample = c->sample;
-    a.sample_count = (u64)s;
-    launch_level(c, a, false, gs);
+    for (int digit = 2; digit <= 3; ++digit) {
+        a = ch.next(kth::ADV_PICK);
+        over_sample(a, c->sample.p, s);
+        launch_level(c, a, false, gs);
+    }
     // the streaming pass
-    a = step(c, kth::ADV_PICK, 0, 1, islot(c, 0), islot(c, 1), islot(c, 2));
-    a.keys = keys;
-    a.n_local = (u64)n;
+    a = ch.next(kth::ADV_PICK);
+    over_keys(a, keys, n);
     ev_main(c);
     launch_main<F32>(c, a, tflag, tflags);
     ev_main(c);
     // decide + candidate (or fallback) levels.  The grids cover the fallback
     // (whole input); in the common case only the WGs the candidates need run.
-    a = step(c, kth::ADV_DECIDE, 1, 0, islot(c, 1), islot(c, 2), islot(c, 0));
-    a.keys = keys;
-    a.n_local = (u64)n;
+    a = ch.next(kth::ADV_DECIDE);
+    over_keys(a, keys, n);
     launch_level<F32>(c, a, true, c->post_dense_grid);
-    a = step(c, kth::ADV_PICK, 0, 1, islot(c, 2), islot(c, 0), islot(c, 1));
-    a.keys = keys;
-    a.n_local = (u64)n;
-    launch_level<F32>(c, a, false, c->post_sparse_grid);
-    a = step(c, kth::ADV_PICK, 1, 0, islot(c, 0), islot(c, 1), islot(c, 2));
-    a.keys = keys;
-    a.n_local = (u64)n;
-    launch_level<F32>(c, a, false, c->post_sparse_grid);
-    a = step(c, kth::ADV_PICK, 0, 1, islot(c, 1), nullptr, nullptr);
-    kth::k_result<F32><<<1, kth::BLK, 0, c->stream>>>(a, d_out, d_status, c->islots, ISLOT_WORDS);
+    for (int digit = 2; digit <= 3; ++digit) {
+        a = ch.next(kth::ADV_PICK);
+        over_keys(a, keys, n);
+        launch_level<F32>(c, a, false, c->post_sparse_grid);
+    }
+    a = ch.next(kth::ADV_PICK, Chain::IN);
+    // k_result clears the slots and the candidate count for the next select --
+    // but a top-k with candidate rows (tflag 3 / 4) still reads the count in
+    // k_topk_cands: there it clears the three slots only and the next select
+    // re-zeroes (dirty).  (It used to clear the count here too, and that top-k
+    // then missed the candidates' share: a bracket failure, nothing written.)
+    const bool keep_count = tflag == 3 || tflag == 4;
+    kth::k_result<F32><<<1, kth::BLK, 0, c->stream>>>(a, d_out, d_status, c->islots,
+                                                     keep_count ? 3 * (u64)kth::STATS_WORDS : (u64)ISLOT_WORDS);
+    if (keep_count) c->dirty = true;
     c->last_state = 1;
     return launch_check();
 }
@@ -656,6 +710,105 @@ int launch_rows(kth_ctx *c, const uint32_t *d_keys, int64_t rows, int32_t cols, 
     return launch_check();
 }
 
+// The four rows entry points: the argument check and the launch.  d_out is the
+// k-th per row (TOPK = false); d_vals / d_idx, either may be null, the top-k.
+template <bool F32, bool TOPK>
+int rows_entry(kth_ctx *c, const void *d_keys, int64_t rows, int32_t cols, int32_t k, void *d_out, int largest = 0,
+               void *d_vals = nullptr, int32_t *d_idx = nullptr) {
+    const bool has_out = TOPK ? d_vals || d_idx : d_out != nullptr;
+    const int32_t max_cols = TOPK ? KTH_TOPK_MAX_COLS : KTH_ROWS_MAX_COLS;
+    if (!c || !d_keys || !has_out || rows < 0 || cols < 1 || cols > max_cols || k < 1 || k > cols) return KTH_EINVAL;
+    if (rows == 0) return KTH_OK;
+    KTH_TRY(set_device(c));
+    return launch_rows<F32, TOPK>(c, static_cast<const uint32_t *>(d_keys), rows, cols, k,
+                                  static_cast<uint32_t *>(d_out), TOPK && largest ? 0xFFFFFFFFu : 0u,
+                                  static_cast<uint32_t *>(d_vals), d_idx);
+}
+
+// ------------------------------------------------------- ctx creation, in parts
+// Every tuning variable of a ctx (design exploration and A/B runs; unset: the
+// defaults in kth_ctx).  Needs c->num_cu.  Read elsewhere: KTH_STAMPS (the
+// stamps diagnostics, kth_ctx_create), KTH_WINDOW_Z (window_z, once a process)
+// and KTH_DEBUG (error messages).
+// (the fault injectors are not read from the environment: only
+// kth_ctx_test_hook, which tests call explicitly, turns them on)
+void read_tuning(kth_ctx *c) {
+    if (const char *g = getenv("KTH_MAIN_WG_PER_CU")) c->main_wg_per_cu = std::max(0, atoi(g));
+    if (const char *g = getenv("KTH_SPARSE_PER_WG")) c->sparse_per_wg = (u64)std::max(0, atoi(g));
+    if (const char *g = getenv("KTH_DSCAN_PER_WG")) c->dscan_per_wg = (u64)std::max(1024, atoi(g));
+    if (const char *g = getenv("KTH_POST_DENSE_GRID")) c->post_dense_grid = std::max(1, atoi(g));
+    if (const char *g = getenv("KTH_POST_SPARSE_GRID")) c->post_sparse_grid = std::max(1, atoi(g));
+    if (const char *g = getenv("KTH_COOP")) c->coop = atoi(g) != 0;
+    if (const char *g = getenv("KTH_PRE_HIST")) c->pre_hist = atoi(g) != 0;
+    c->fin_grid = c->num_cu;
+    if (const char *g = getenv("KTH_FIN_GRID")) c->fin_grid = std::max(1, std::min(atoi(g), c->num_cu));
+    if (const char *g = getenv("KTH_HEAD_SLACK")) c->head_slack64 = (uint32_t)std::max(0.0, atof(g) * 64.0);
+    if (const char *g = getenv("KTH_HEAD_ABS")) c->head_abs_div = (uint32_t)std::max(0, atoi(g));
+    if (const char *g = getenv("KTH_TOPK_STAGE")) c->topk_stage = atoi(g) != 0;
+}
+
+// k_main<TF, F32>'s address; null for the float32 staged variants, which are not built
+template <int TF, bool F32>
+const void *main_fn() {
+    if constexpr (F32 && TF >= 5)
+        return nullptr;
+    else
+        return reinterpret_cast<const void *>(kth::k_main<TF, F32>);
+}
+template <bool F32>
+std::array<const void *, 7> main_fns() {
+    return {main_fn<0, F32>(), main_fn<1, F32>(), main_fn<2, F32>(), main_fn<3, F32>(),
+            main_fn<4, F32>(), main_fn<5, F32>(), main_fn<6, F32>()};
+}
+
+// One resident wave of workgroups: every WG streams an equal share
+// and no tail of late WGs.  Residency from each k_main variant's own
+// VGPR and LDS use (4 waves per 256-thread WG = one per SIMD; a SIMD
+// holds 512 / alloc(VGPR) waves, MI355X_MICROARCH.md register files);
+// the top-k variants keep more keys live and may allocate more VGPRs.
+// hipOccupancyMaxActiveBlocksPerMultiprocessor under-reports here.
+void size_main_grids(kth_ctx *c) {
+    const std::array<const void *, 7> fns[2] = {main_fns<false>(), main_fns<true>()};  // [key kind][TF], as c->main_grid
+    for (int kind = 0; kind < 2; ++kind)
+        for (int tf = 0; tf < 7; ++tf) {
+            if (!fns[kind][tf]) continue;
+            int per = 4;
+            hipFuncAttributes fa;
+            if (hipFuncGetAttributes(&fa, fns[kind][tf]) == hipSuccess && fa.numRegs > 0) {
+                const int alloc = (fa.numRegs + 7) / 8 * 8;
+                const int by_vgpr = std::min(8, 512 / alloc);
+                const int lds = (int)fa.sharedSizeBytes;
+                const int by_lds = lds > 0 ? (160 * 1024) / lds : 8;
+                per = std::max(1, std::min(by_vgpr, by_lds));
+            }
+            (void)hipGetLastError();
+            if (c->main_wg_per_cu > 0) per = c->main_wg_per_cu;
+            c->main_grid[kind][tf] = c->num_cu * per;
+        }
+}
+
+// Workgroups a CU holds of k_finish<F32> and k_head<F32>; false when the
+// occupancy query is unavailable.
+template <bool F32>
+bool coop_per_cu(int *fin, int *head) {
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(fin, reinterpret_cast<const void *>(kth::k_finish<F32>),
+                                                        kth::DENSE_BLK, FIN_DYN_LDS) == hipSuccess &&
+           hipOccupancyMaxActiveBlocksPerMultiprocessor(head, reinterpret_cast<const void *>(kth::k_head<F32>),
+                                                        kth::DENSE_BLK, 0) == hipSuccess;
+}
+
+// Can the device hold k_finish's and k_head's grids at once?
+// (both key kinds share the ctx's one coop switch: the smaller of
+// the int32 and float32 instantiations' figures decides)
+bool coop_grids_resident(const kth_ctx *c) {
+    int fin[2] = {0, 0}, head[2] = {0, 0};
+    const bool known = coop_per_cu<false>(&fin[0], &head[0]) && coop_per_cu<true>(&fin[1], &head[1]);
+    (void)hipGetLastError();
+    if (!known) return true;  // query unavailable: trust the static sizing
+    return (int64_t)std::min(fin[0], fin[1]) * c->num_cu >= c->fin_grid &&
+           (int64_t)std::min(head[0], head[1]) * c->num_cu >= HEAD_GRID_MAX;
+}
+
 }  // namespace
 
 // ====================================================================== API
@@ -711,55 +864,8 @@ int kth_ctx_create(int device, kth_ctx **out) {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
             c->num_cu = prop.multiProcessorCount;
-        {
-            // One resident wave of workgroups: every WG streams an equal share
-            // and no tail of late WGs.  Residency from each k_main variant's own
-            // VGPR and LDS use (4 waves per 256-thread WG = one per SIMD; a SIMD
-            // holds 512 / alloc(VGPR) waves, MI355X_MICROARCH.md register files);
-            // the top-k variants keep more keys live and may allocate more VGPRs.
-            // hipOccupancyMaxActiveBlocksPerMultiprocessor under-reports here.
-            const void *fns[7] = {reinterpret_cast<const void *>(kth::k_main<0>),
-                                  reinterpret_cast<const void *>(kth::k_main<1>),
-                                  reinterpret_cast<const void *>(kth::k_main<2>),
-                                  reinterpret_cast<const void *>(kth::k_main<3>),
-                                  reinterpret_cast<const void *>(kth::k_main<4>),
-                                  reinterpret_cast<const void *>(kth::k_main<5>),
-                                  reinterpret_cast<const void *>(kth::k_main<6>)};
-            // float32 keys: k_main<TF, true>, TF 0..4 (after the int32 ones)
-            const void *fns_f32[5] = {reinterpret_cast<const void *>(kth::k_main<0, true>),
-                                      reinterpret_cast<const void *>(kth::k_main<1, true>),
-                                      reinterpret_cast<const void *>(kth::k_main<2, true>),
-                                      reinterpret_cast<const void *>(kth::k_main<3, true>),
-                                      reinterpret_cast<const void *>(kth::k_main<4, true>)};
-            const char *e = getenv("KTH_MAIN_WG_PER_CU");
-            for (int v = 0; v < 12; ++v) {
-                int per = 4;
-                hipFuncAttributes fa;
-                if (hipFuncGetAttributes(&fa, v < 7 ? fns[v] : fns_f32[v - 7]) == hipSuccess && fa.numRegs > 0) {
-                    const int alloc = (fa.numRegs + 7) / 8 * 8;
-                    const int by_vgpr = std::min(8, 512 / alloc);
-                    const int lds = (int)fa.sharedSizeBytes;
-                    const int by_lds = lds > 0 ? (160 * 1024) / lds : 8;
-                    per = std::max(1, std::min(by_vgpr, by_lds));
-                }
-                (void)hipGetLastError();
-                if (e && atoi(e) > 0) per = atoi(e);
-                (v < 7 ? c->main_grid[v] : c->main_grid_f32[v - 7]) = c->num_cu * per;
-            }
-            if (const char *g = getenv("KTH_SPARSE_PER_WG")) c->sparse_per_wg = (u64)std::max(0, atoi(g));
-            if (const char *g = getenv("KTH_DSCAN_PER_WG")) c->dscan_per_wg = (u64)std::max(1024, atoi(g));
-            if (const char *g = getenv("KTH_POST_DENSE_GRID")) c->post_dense_grid = std::max(1, atoi(g));
-            if (const char *g = getenv("KTH_POST_SPARSE_GRID")) c->post_sparse_grid = std::max(1, atoi(g));
-            if (const char *g = getenv("KTH_COOP")) c->coop = atoi(g) != 0;
-            if (const char *g = getenv("KTH_PRE_HIST")) c->pre_hist = atoi(g) != 0;
-            c->fin_grid = c->num_cu;
-            if (const char *g = getenv("KTH_FIN_GRID")) c->fin_grid = std::max(1, std::min(atoi(g), c->num_cu));
-            if (const char *g = getenv("KTH_HEAD_SLACK")) c->head_slack64 = (uint32_t)std::max(0.0, atof(g) * 64.0);
-            if (const char *g = getenv("KTH_HEAD_ABS")) c->head_abs_div = (uint32_t)std::max(0, atoi(g));
-            if (const char *g = getenv("KTH_TOPK_STAGE")) c->topk_stage = atoi(g) != 0;
-            // (the fault injectors are not read from the environment: only
-            // kth_ctx_test_hook, which tests call explicitly, turns them on)
-        }
+        read_tuning(c);
+        size_main_grids(c);
         if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { rc = KTH_EHIP; break; }
         c->own_stream = true;
         if (hipMalloc(reinterpret_cast<void **>(&c->st), 2 * sizeof(SelState)) != hipSuccess ||
@@ -803,31 +909,9 @@ int kth_ctx_create(int device, kth_ctx **out) {
         // COOP_BACKOFF synchronous selects.  The asynchronous entry points
         // (kth_select_i32_async, kth_topk_i32, kth_dist_*) report the error in
         // the state (kth_ctx_last_stats) and leave the retry to the caller.
-        {
-            // (both key kinds share the ctx's one coop switch: the smaller of
-            // the int32 and float32 instantiations' figures decides)
-            const void *fin_fns[2] = {reinterpret_cast<const void *>(kth::k_finish<false>),
-                                      reinterpret_cast<const void *>(kth::k_finish<true>)};
-            const void *head_fns[2] = {reinterpret_cast<const void *>(kth::k_head<false>),
-                                       reinterpret_cast<const void *>(kth::k_head<true>)};
-            int fin_per_cu = INT32_MAX, head_per_cu = INT32_MAX;
-            for (int f = 0; f < 2 && fin_per_cu >= 0; ++f) {
-                int fin = 0, head = 0;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&fin, fin_fns[f], kth::DENSE_BLK, FIN_DYN_LDS) !=
-                        hipSuccess ||
-                    hipOccupancyMaxActiveBlocksPerMultiprocessor(&head, head_fns[f], kth::DENSE_BLK, 0) != hipSuccess) {
-                    fin_per_cu = head_per_cu = -1;  // query unavailable: trust the static sizing
-                } else {
-                    fin_per_cu = std::min(fin_per_cu, fin);
-                    head_per_cu = std::min(head_per_cu, head);
-                }
-            }
-            (void)hipGetLastError();
-            if (fin_per_cu >= 0 &&
-                ((int64_t)fin_per_cu * c->num_cu < c->fin_grid || (int64_t)head_per_cu * c->num_cu < HEAD_GRID_MAX)) {
-                c->coop = false;
-                c->coop_resident = false;
-            }
+        if (!coop_grids_resident(c)) {
+            c->coop = false;
+            c->coop_resident = false;
         }
     } while (0);
     c->coop_wanted = c->coop;
@@ -864,15 +948,8 @@ int kth_ctx_destroy(kth_ctx *c) {
     for (hipEvent_t e : c->ev_total) (void)hipEventDestroy(e);
     if (c->st) (void)hipFree(c->st);
     if (c->islots) (void)hipFree(c->islots);
-    if (c->sample) (void)hipFree(c->sample);
-    if (c->cand) (void)hipFree(c->cand);
-    if (c->cand_rows) (void)hipFree(c->cand_rows);
-    if (c->tk_segv) (void)hipFree(c->tk_segv);
-    if (c->tk_segp) (void)hipFree(c->tk_segp);
-    if (c->tk_wcnt) (void)hipFree(c->tk_wcnt);
-    if (c->tk_wstart) (void)hipFree(c->tk_wstart);
-    if (c->staging) (void)hipFree(c->staging);
-    if (c->topk) (void)hipFree(c->topk);
+    release_all(c->sample, c->cand, c->cand_rows, c->tk_segv, c->tk_segp, c->tk_wcnt, c->tk_wstart, c->staging,
+                c->topk);
     if (c->d_status) (void)hipFree(c->d_status);
     if (c->stamps) (void)hipFree(c->stamps);
     if (c->h_status) (void)hipHostFree(c->h_status);
@@ -910,11 +987,7 @@ int kth_ctx_sync(kth_ctx *c) {
 int kth_ctx_reserve(kth_ctx *c, int64_t n) {
     if (!c || n < 0) return KTH_EINVAL;
     KTH_TRY(set_device(c));
-    if (n > RADIX_MAX_N) {
-        KTH_TRY(grow(reinterpret_cast<void **>(&c->sample), &c->sample_cap, (u64)sample_size(n) * 4));
-        KTH_TRY(reserve_cand(c, n));
-    }
-    return KTH_OK;
+    return n > RADIX_MAX_N ? reserve_window(c, n) : KTH_OK;
 }
 
 int kth_select_i32_async(kth_ctx *c, const int32_t *d_keys, int64_t n, int64_t k, int32_t *d_out) {
@@ -932,6 +1005,15 @@ int kth_select_f32_async(kth_ctx *c, const float *d_keys, int64_t n, int64_t k, 
 
 namespace {
 
+// One select into d_status, and [answer, error] fetched into h_status.
+template <bool F32>
+int select_fetch(kth_ctx *c, const int32_t *dk, int64_t n, int64_t k) {
+    KTH_TRY(select_async<F32>(c, dk, n, k, nullptr, c->d_status));
+    HIP_TRY(hipMemcpyAsync(c->h_status, c->d_status, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return KTH_OK;
+}
+
 // The synchronous select through a ctx, either key kind (the words travel as
 // int32; *out receives the caller's word: for float32 the answer's bits).
 template <bool F32>
@@ -940,13 +1022,11 @@ int select_ctx(kth_ctx *c, const int32_t *keys, int64_t n, int64_t k, int32_t *o
     KTH_TRY(set_device(c));
     const int32_t *dk = keys;
     if (!is_device_ptr(keys)) {
-        KTH_TRY(grow(reinterpret_cast<void **>(&c->staging), &c->staging_cap, (u64)n * 4));
-        HIP_TRY(hipMemcpyAsync(c->staging, keys, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-        dk = c->staging;
+        KTH_TRY(c->staging.reserve((u64)n));
+        HIP_TRY(hipMemcpyAsync(c->staging.p, keys, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        dk = c->staging.p;
     }
-    KTH_TRY(select_async<F32>(c, dk, n, k, nullptr, c->d_status));
-    HIP_TRY(hipMemcpyAsync(c->h_status, c->d_status, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    KTH_TRY(select_fetch<F32>(c, dk, n, k));
     if (c->h_status[1] == (int32_t)kth::ERR_BARRIER && c->coop) {
         // a cooperative grid was not co-resident (another stream or process
         // held CUs): redo the select on the per-level path, which needs no
@@ -956,9 +1036,7 @@ int select_ctx(kth_ctx *c, const int32_t *keys, int64_t n, int64_t k, int32_t *o
         c->dirty = true;
         c->coop = false;
         c->coop_backoff = COOP_BACKOFF + 1;  // (the retry below counts one)
-        KTH_TRY(select_async<F32>(c, dk, n, k, nullptr, c->d_status));
-        HIP_TRY(hipMemcpyAsync(c->h_status, c->d_status, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
+        KTH_TRY(select_fetch<F32>(c, dk, n, k));
     }
     if (c->h_status[1] != 0) {
         c->dirty = true;
@@ -1042,7 +1120,7 @@ int kth_ctx_last_stats(kth_ctx *c, kth_stats *out) {
     out->cnt_eq_lo = s.cnt[kth::C_EQLO];
     out->cnt_eq_hi = s.cnt[kth::C_EQHI];
     out->candidates = s.cnt[kth::C_IN];
-    out->capacity = c->cand_cap / 4;
+    out->capacity = c->cand.count;
     out->answer = c->last_f32 ? (int32_t)kth::f32_of_key(s.answer) : (int32_t)(s.answer ^ 0x80000000u);
     out->error = (int32_t)s.error;
     return KTH_OK;
@@ -1087,43 +1165,21 @@ int kth_ctx_take_timing(kth_ctx *c, int64_t *n_sel, double *main_ms, double *tot
 }
 
 int kth_select_rows_i32(kth_ctx *c, const int32_t *d_keys, int64_t rows, int32_t cols, int32_t k, int32_t *d_out) {
-    if (!c || !d_keys || !d_out || rows < 0 || cols < 1 || cols > KTH_ROWS_MAX_COLS || k < 1 || k > cols)
-        return KTH_EINVAL;
-    if (rows == 0) return KTH_OK;
-    KTH_TRY(set_device(c));
-    return launch_rows<false, false>(c, reinterpret_cast<const uint32_t *>(d_keys), rows, cols, k,
-                              reinterpret_cast<uint32_t *>(d_out));
+    return rows_entry<false, false>(c, d_keys, rows, cols, k, d_out);
 }
 
 int kth_select_rows_f32(kth_ctx *c, const float *d_keys, int64_t rows, int32_t cols, int32_t k, float *d_out) {
-    if (!c || !d_keys || !d_out || rows < 0 || cols < 1 || cols > KTH_ROWS_MAX_COLS || k < 1 || k > cols)
-        return KTH_EINVAL;
-    if (rows == 0) return KTH_OK;
-    KTH_TRY(set_device(c));
-    return launch_rows<true, false>(c, reinterpret_cast<const uint32_t *>(d_keys), rows, cols, k,
-                             reinterpret_cast<uint32_t *>(d_out));
+    return rows_entry<true, false>(c, d_keys, rows, cols, k, d_out);
 }
 
 int kth_topk_rows_i32(kth_ctx *c, const int32_t *d_keys, int64_t rows, int32_t cols, int32_t k, int largest,
                       int32_t *d_vals, int32_t *d_idx) {
-    if (!c || !d_keys || (!d_vals && !d_idx) || rows < 0 || cols < 1 || cols > KTH_TOPK_MAX_COLS || k < 1 ||
-        k > cols)
-        return KTH_EINVAL;
-    if (rows == 0) return KTH_OK;
-    KTH_TRY(set_device(c));
-    return launch_rows<false, true>(c, reinterpret_cast<const uint32_t *>(d_keys), rows, cols, k, nullptr,
-                                    largest ? 0xFFFFFFFFu : 0u, reinterpret_cast<uint32_t *>(d_vals), d_idx);
+    return rows_entry<false, true>(c, d_keys, rows, cols, k, nullptr, largest, d_vals, d_idx);
 }
 
 int kth_topk_rows_f32(kth_ctx *c, const float *d_keys, int64_t rows, int32_t cols, int32_t k, int largest,
                       float *d_vals, int32_t *d_idx) {
-    if (!c || !d_keys || (!d_vals && !d_idx) || rows < 0 || cols < 1 || cols > KTH_TOPK_MAX_COLS || k < 1 ||
-        k > cols)
-        return KTH_EINVAL;
-    if (rows == 0) return KTH_OK;
-    KTH_TRY(set_device(c));
-    return launch_rows<true, true>(c, reinterpret_cast<const uint32_t *>(d_keys), rows, cols, k, nullptr,
-                                   largest ? 0xFFFFFFFFu : 0u, reinterpret_cast<uint32_t *>(d_vals), d_idx);
+    return rows_entry<true, true>(c, d_keys, rows, cols, k, nullptr, largest, d_vals, d_idx);
 }
 
 }  // extern "C"
@@ -1166,24 +1222,21 @@ int topk_impl(kth_ctx *c, const int32_t *d_keys, int64_t n, int64_t k, int large
     // tflags: the header and TF 1 / 2's flag bytes after 4 words, TF >= 3's
     // row words after TF_W0 in per-wave segments (kth::rw_index); 256-byte
     // aligned, so that a wave's group of 64 words fills one line
-    const u64 Gm = (u64)(F32 ? c->main_grid_f32[tf] : c->main_grid[tf]);
+    const u64 Gm = (u64)c->main_grid[F32][tf];  // k_main<tf, F32>'s workgroups
     const kth::RowWords rwl{Gm, tf >= 3 ? kth::rw_seg_words(nfull, Gm) : kth::fl_seg_bytes(nfull, Gm)};
     const u64 fwords = tf >= 3 ? kth::TF_W0 + rwl.G * (kth::BLK / kth::WAVE) * rwl.seg
                                : 4 + rwl.G * (kth::BLK / kth::WAVE) * rwl.seg / 4;
     const u64 fw64 = (fwords + 1) / 2, before = (ntiles + 1) / 2 + ntiles + 4 * nblk + 2;
     const u64 words = before + fw64 + 32;
-    KTH_TRY(grow(reinterpret_cast<void **>(&c->topk), &c->topk_cap, words * sizeof(u64)));
+    KTH_TRY(c->topk.reserve(words));
     const u64 foff = (before + 31) & ~31ull;  // + fw64 <= words
-    uint32_t *tflags = reinterpret_cast<uint32_t *>(c->topk + foff);
+    uint32_t *tflags = reinterpret_cast<uint32_t *>(c->topk.p + foff);
     HIP_TRY(hipMemsetAsync(tflags, 0, 16, c->stream));  // window header: not valid until k_main<TF> runs
-    if (tf == 3 || tf == 4) {
-        KTH_TRY(reserve_cand(c, n));
-        KTH_TRY(grow(reinterpret_cast<void **>(&c->cand_rows), &c->cand_rows_cap, c->cand_cap));
-    }
+    if (tf == 3 || tf == 4) KTH_TRY(reserve_cand(c, n, true));
     u64 seg_cap = 0;
     uint32_t nwin = 0;
     if (tf >= 5) {  // the staging segments: one per k_main wave, n / 16 entries in all
-        const u64 nwaves = (u64)c->main_grid[tf] * (kth::BLK / kth::WAVE);
+        const u64 nwaves = Gm * (kth::BLK / kth::WAVE);
         // entries: the k kept keys, the candidates (~0.6 % of n at 2^30) and the
         // waves' imbalance; a segment that overflows sends the top-k to the
         // input-reading path (exact)
@@ -1191,19 +1244,18 @@ int topk_impl(kth_ctx *c, const int32_t *d_keys, int64_t n, int64_t k, int large
         seg_cap = c->topk_seg_cap ? c->topk_seg_cap : (seg_total + nwaves - 1) / nwaves;
         seg_cap = (seg_cap + 3) & ~3ull;  // segments start 16-byte aligned (k_main<5/6> stores 4 entries a lane)
         KTH_TRY(reserve_cand(c, n));
-        KTH_TRY(grow(reinterpret_cast<void **>(&c->tk_segv), &c->tk_segv_cap, seg_cap * nwaves * 4));
-        KTH_TRY(grow(reinterpret_cast<void **>(&c->tk_segp), &c->tk_segp_cap, seg_cap * nwaves));
-        KTH_TRY(grow(reinterpret_cast<void **>(&c->tk_wcnt), &c->tk_wcnt_cap, ncov * (kth::BLK / kth::WAVE) * 4 + 16));
+        KTH_TRY(c->tk_segv.reserve(seg_cap * nwaves));
+        KTH_TRY(c->tk_segp.reserve(seg_cap * nwaves));
+        KTH_TRY(c->tk_wcnt.reserve(ncov * (kth::BLK / kth::WAVE) + 4));
         // per wave and window (TK5_WIN_TILES of its tiles): the entries staged before it
-        const u64 G = (u64)c->main_grid[tf];
-        nwin = (uint32_t)(((nfull + G - 1) / G + kth::TK5_WIN_TILES - 1) / kth::TK5_WIN_TILES);
-        KTH_TRY(grow(reinterpret_cast<void **>(&c->tk_wstart), &c->tk_wstart_cap, nwaves * std::max(nwin, 1u) * 4));
+        nwin = (uint32_t)(((nfull + Gm - 1) / Gm + kth::TK5_WIN_TILES - 1) / kth::TK5_WIN_TILES);
+        KTH_TRY(c->tk_wstart.reserve(nwaves * std::max(nwin, 1u)));
         // dense staging (k >= n / 32) stores the segments non-temporally: k_main<5> at k = 2^26 964-976
         // against 980-984 us, whole calls -0.5 to -2 %; at k = 2^24 k_main<5> gains ~6 us but
         // k_tk5_count, which then reads the entries from HBM, loses ~8; at 2^20 +0.8 %
         // (profiles/r6_topk_seg_store_ab.txt)
         const uint32_t nt = (u64)k * 32 >= (u64)n ? 1u : 0u;
-        c->tk_seg = kth::TkSeg{c->tk_segv, c->tk_segp, (uint32_t)seg_cap, tflags + 3, c->tk_wstart, nwin, nt};
+        c->tk_seg = kth::TkSeg{c->tk_segv.p, c->tk_segp.p, (uint32_t)seg_cap, tflags + 3, c->tk_wstart.p, nwin, nt};
     }
     // the k-th smallest (largest: the (n-k+1)-th smallest) -> d_status[0], on the device
     int64_t rank = largest ? n - k + 1 : k;
@@ -1211,7 +1263,7 @@ int topk_impl(kth_ctx *c, const int32_t *d_keys, int64_t n, int64_t k, int large
     KTH_TRY(select_async<F32>(c, d_keys, n, rank, nullptr, c->d_status, tf, tflags));
     const uint32_t *keys = reinterpret_cast<const uint32_t *>(d_keys);
     const uint32_t flip = largest ? 0xFFFFFFFFu : 0u;
-    u64 *toff = c->topk, *bsum = toff + ntiles, *bbase = bsum + 2 * nblk, *meta = bbase + 2 * nblk;
+    u64 *toff = c->topk.p, *bsum = toff + ntiles, *bbase = bsum + 2 * nblk, *meta = bbase + 2 * nblk;
     uint32_t *tcnt = reinterpret_cast<uint32_t *>(meta + 2);
     const SelState *sel_st = c->st + c->last_state;
     // count and write passes: one wave per 64 tiles
@@ -1219,15 +1271,14 @@ int topk_impl(kth_ctx *c, const int32_t *d_keys, int64_t n, int64_t k, int large
     const int g = (int)std::min<u64>((ntiles + waves * kth::WAVE - 1) / (waves * kth::WAVE), (u64)c->num_cu * 16);
     if (tf >= 5) {  // the staged entries (rows < ncov), then the ragged rows from the input
         auto tk5c = (u64)k * 64 >= (u64)n ? kth::k_tk5_count<true> : kth::k_tk5_count<false>;  // dense windows: chunked
-        tk5c<<<c->main_grid[tf] * TK5_SPLIT, kth::TK_BLOCK, 0, c->stream>>>(
-            c->tk_segv, seg_cap, c->tk_wstart, nwin, (u64)c->main_grid[tf], tflags, nfull, c->d_status, flip,
-            c->tk_wcnt, tcnt);
+        tk5c<<<(int)Gm * TK5_SPLIT, kth::TK_BLOCK, 0, c->stream>>>(
+            c->tk_segv.p, seg_cap, c->tk_wstart.p, nwin, Gm, tflags, nfull, c->d_status, flip, c->tk_wcnt.p, tcnt);
         kth::k_topk_count<true, 2><<<g, kth::TK_BLOCK, 0, c->stream>>>(keys, (u64)n, ntiles, c->d_status, flip, tcnt,
                                                                        tflags, head, nfull, sel_st, ncov);
     } else if (tf >= 3) {  // candidates' share first (atomics into zeroed counts), then the rows' words
         HIP_TRY(hipMemsetAsync(tcnt, 0, ntiles * 4, c->stream));
         kth::k_topk_cands<<<c->num_cu * 8, kth::TK_BLOCK, 0, c->stream>>>(
-            c->cand, c->cand_rows, cand_count(c), c->cand_cap / 4, c->d_status, flip, tcnt, tflags, sel_st);
+            c->cand.p, c->cand_rows.p, cand_count(c), c->cand.count, c->d_status, flip, tcnt, tflags, sel_st);
         kth::k_topk_count<true, 1, F32><<<g, kth::TK_BLOCK, 0, c->stream>>>(
             keys, (u64)n, ntiles, c->d_status, flip, tcnt, tflags, head, nfull, sel_st, ncov, rwl);
     } else if (aligned) {
@@ -1245,9 +1296,9 @@ int topk_impl(kth_ctx *c, const int32_t *d_keys, int64_t n, int64_t k, int large
         reinterpret_cast<uint32_t *>(c->islots + BAR_OFF) + kth::BAR_TOPK_ARRIVE);
     if (tf >= 5) {
         auto tk5w = (u64)k * 32 <= (u64)n ? kth::k_tk5_write<kth::TK5_STAGE_SMALL> : kth::k_tk5_write<kth::TK5_STAGE_LARGE>;
-        tk5w<<<c->main_grid[tf] * TK5_SPLIT, kth::TK_BLOCK, 0, c->stream>>>(
-            c->tk_segv, c->tk_segp, seg_cap, c->tk_wstart, nwin, (u64)c->main_grid[tf], tflags, nfull, c->d_status,
-            flip, c->tk_wcnt, tcnt, toff, bbase, meta, d_vals, d_idx);
+        tk5w<<<(int)Gm * TK5_SPLIT, kth::TK_BLOCK, 0, c->stream>>>(
+            c->tk_segv.p, c->tk_segp.p, seg_cap, c->tk_wstart.p, nwin, Gm, tflags, nfull, c->d_status, flip,
+            c->tk_wcnt.p, tcnt, toff, bbase, meta, d_vals, d_idx);
         kth::k_topk_write<true, true><<<g, kth::TK_BLOCK, 0, c->stream>>>(keys, (u64)n, ntiles, c->d_status, flip,
                                                                           tcnt, toff, bbase, meta, d_vals, d_idx,
                                                                           tflags, ncov);
@@ -1368,39 +1419,30 @@ int kth_dist_window(kth_ctx *c, const uint32_t *d_sample, int64_t s_total) {
         // gather): the digits behind grid barriers, the early window; the state
         // is left resolved in st[0] for kth_dist_scan (ADV_CARRY).  Its slots
         // are cleared by kth_dist_result's k_result.
-        StepArgs a = step(c, kth::ADV_INIT_SAMPLE, -1, 0, nullptr, nullptr, nullptr);
-        a.init_n = (u64)c->dist_n;
-        a.init_k = (u64)c->dist_k;
-        a.init_s = (u64)s_total;
-        a.r_lo = r_lo;
-        a.r_hi = r_hi;
+        Chain ch{c, c->islots, 2};
+        StepArgs a = head_step(ch, c->dist_n, c->dist_k, s_total, r_lo, r_hi, false);
         kth::CoopArgs x = coop_args(c, HSLOT_OFF, nullptr, nullptr);
         x.sample_ready = 1;
-        const int grid = (int)std::min<int64_t>(64, std::max<int64_t>(1, s_total / (16 * 1024)));
+        const int grid = (int)std::min<int64_t>(HEAD_GRID_MAX, std::max<int64_t>(1, s_total / HEAD_PER_WG));
         kth::k_head<false><<<grid, kth::DENSE_BLK, 0, c->stream>>>(a, x, nullptr, 0, 0,
                                                                   const_cast<uint32_t *>(d_sample), (u64)s_total);
         c->dist_coop_window = true;
         return launch_check();
     }
     c->dist_coop_window = false;
-    StepArgs a = step(c, kth::ADV_INIT_SAMPLE, -1, 0, nullptr, islot(c, 1), islot(c, 2));
-    a.init_n = (u64)c->dist_n;
-    a.init_k = (u64)c->dist_k;
-    a.init_s = (u64)s_total;
-    a.r_lo = r_lo;
-    a.r_hi = r_hi;
-    a.sample = d_sample;
-    a.sample_count = (u64)s_total;
+    // the three digits of the sample ranks, a launch each (steps 0 to 2;
+    // kth_dist_scan's pass is step 3)
+    Chain ch{c, c->islots};
+    StepArgs a = ch.next(kth::ADV_INIT_SAMPLE, Chain::ACC | Chain::ZERO);
+    init_rank(a, c->dist_n, c->dist_k, s_total, r_lo, r_hi);
+    over_sample(a, d_sample, s_total);
     launch_level(c, a, true, level_grid((u64)s_total, DENSE_PER_WG));
     const int gs = level_grid((u64)s_total, sparse_wg(c));
-    a = step(c, kth::ADV_PICK, 0, 1, islot(c, 1), islot(c, 2), islot(c, 0));
-    a.sample = d_sample;
-    a.sample_count = (u64)s_total;
-    launch_level(c, a, false, gs);
-    a = step(c, kth::ADV_PICK, 1, 0, islot(c, 2), islot(c, 0), islot(c, 1));
-    a.sample = d_sample;
-    a.sample_count = (u64)s_total;
-    launch_level(c, a, false, gs);
+    for (int digit = 2; digit <= 3; ++digit) {
+        a = ch.next(kth::ADV_PICK);
+        over_sample(a, d_sample, s_total);
+        launch_level(c, a, false, gs);
+    }
     return launch_check();
 }
 
@@ -1409,12 +1451,15 @@ int kth_dist_scan(kth_ctx *c, const int32_t *d_keys, int64_t n_local) {
     KTH_TRY(set_device(c));
     KTH_TRY(reserve_cand(c, std::max<int64_t>(n_local, 1)));
     u64 *U0 = c->uslots;
-    StepArgs a = c->dist_coop_window ? step(c, kth::ADV_CARRY, 0, 1, nullptr, U0, nullptr)
-                                     : step(c, kth::ADV_PICK, 0, 1, islot(c, 0), U0, nullptr);
-    a.keys = d_keys;
-    a.n_local = (u64)n_local;
+    // step 3 of the window's chain over the ctx's slots (k_head resolved its
+    // digits itself; the per-level window left the last one in islot(0)); the
+    // counts go straight into the all-reduced slot 0 instead of islot(1)
+    Chain ch{c, c->islots, 3};
+    StepArgs a = c->dist_coop_window ? ch.next(kth::ADV_CARRY, Chain::NONE) : ch.next(kth::ADV_PICK, Chain::IN);
+    a.stats_acc = U0;
+    over_keys(a, d_keys, n_local);
     ev_main(c);
-    kth::k_main<0><<<c->main_grid[0], kth::BLK, 0, c->stream>>>(a, c->cand, nullptr, nullptr, kth::TkSeg{});
+    launch_main<false>(c, a, 0, nullptr);
     ev_main(c);
     KTH_TRY(launch_check());
     // this rank's candidates' first digit into the same slot (one all-reduce
@@ -1429,8 +1474,8 @@ int kth_dist_scan(kth_ctx *c, const int32_t *d_keys, int64_t n_local) {
     return 0;
 }
 
-// Level l reads state l+1 (mod 2) and slot l (mod 3), writes state l (mod 2),
-// accumulates into slot l+1 and clears slot l+2; level 0 also tells the host
+// Level l is step l of a chain over the bound slots (it accumulates into slot
+// l+1 mod 3, which the caller all-reduces); level 0 also tells the host
 // (DistStatus) how many level calls return a slot, so that level 1 can answer
 // KTH_DIST_DONE without a collective.  Level 0 is enqueued without waiting
 // for anything; level 1 waits for level 0 (the host reads the DistStatus) --
@@ -1453,12 +1498,8 @@ int kth_dist_level(kth_ctx *c, const int32_t *d_keys, int64_t n_local, int level
         c->dist_level_next = -1;
         return KTH_DIST_DONE;
     }
-    u64 *U[3] = {c->uslots, c->uslots + KTH_STATS_WORDS, c->uslots + 2 * KTH_STATS_WORDS};
-    const int in = level % 3, acc = (level + 1) % 3, zero = (level + 2) % 3;
-    StepArgs a = step(c, level == 0 ? kth::ADV_DECIDE : kth::ADV_PICK, (level + 1) % 2, level % 2, U[in], U[acc],
-                      U[zero]);
-    a.keys = d_keys;
-    a.n_local = (u64)n_local;
+    StepArgs a = Chain{c, c->uslots, level}.next(level == 0 ? kth::ADV_DECIDE : kth::ADV_PICK);
+    over_keys(a, d_keys, n_local);
     a.min_per_wg = sparse_wg(c);     // a digit under a resolved prefix: only that bin's keys
     a.dense_per_wg = DENSE_PER_WG;   // the fallback's first digit over the whole shard
     if (level == 0) {
@@ -1470,7 +1511,7 @@ int kth_dist_level(kth_ctx *c, const int32_t *d_keys, int64_t n_local, int level
     KTH_TRY(launch_check());
     if (level == 0) HIP_TRY(hipEventRecord(c->ev_dist, c->stream));
     c->dist_level_next = level + 1;
-    return acc;
+    return (level + 1) % 3;  // the slot it accumulated into
 }
 
 int kth_internal_slots_sum(uint64_t *const *slots, int P, int slot, void *stream) {
@@ -1519,16 +1560,14 @@ int kth_internal_dist_window_share(kth_ctx *src, kth_ctx *const *dst, int P) {
     return KTH_OK;
 }
 
-// k_dresult after L levels: state (L + 1) % 2 and slot L % 3 in, the other state out
+// k_dresult after L levels: step L of their chain (state (L + 1) % 2 and slot L % 3 in, the other state out)
 static int launch_dresult(kth_ctx *c, int L, int32_t *d_out, uint32_t early) {
-    const int st_in = (L + 1) % 2;
-    StepArgs a = step(c, kth::ADV_PICK, st_in, 1 - st_in, c->uslots + (size_t)(L % 3) * KTH_STATS_WORDS,
-                      nullptr, nullptr);
+    StepArgs a = Chain{c, c->uslots, L}.next(kth::ADV_PICK, Chain::IN);
     // (the islots and, right after them, k_head's slots of a cooperative window)
     static_assert(ISLOT_WORDS % 2 == 0, "k_dresult zeroes 16-byte words from the islots on");
     kth::k_dresult<kth::BLK><<<16, kth::BLK, 0, c->stream>>>(a, d_out, c->d_status, c->islots,
                                                             ISLOT_WORDS + HSLOT_WORDS, early);
-    c->last_state = 1 - st_in;
+    c->last_state = L % 2;
     c->last_f32 = false;  // (the sharded protocol is int32 only)
     return launch_check();
 }

@@ -15,6 +15,8 @@
 * Grid-barrier timeouts (the test-only KTH_HOOK_FAULT_BARRIER): reported in the state, d_out left
   untouched by the asynchronous entry, and the synchronous entry redoes the
   select on the per-level path.
+* The per-level launch sequences that only run while a ctx backs off after such
+  a timeout: top-k with each kind of k_main record and the sharded steps.
 """
 import contextlib
 
@@ -161,6 +163,48 @@ def test_coop_backoff_counts_every_entry_point(gpu):
         assert sel.coop()
         sel.sync()
         assert int(out.item()) == srt[n // 3 - 1] and sel.stats()["error"] == 0
+    finally:
+        sel.close()
+
+
+def test_backoff_runs_every_per_level_sequence(gpu):
+    """While a ctx backs off after a grid-barrier timeout, every entry point
+    takes its per-level launch sequence: the window select, a top-k over it
+    with each kind of k_main record (flags, staged, row words), and the sharded
+    steps (kth_dist_window level by level, kth_dist_scan's ADV_PICK pass).  The
+    back-off lasts 64 selections; this test uses about ten and checks after
+    each call that the ctx is still off the cooperative path."""
+    import torch
+    import kselect
+    from kselect.dist import DistSelector, HipBackend
+    sel = kselect.Selector(0)
+    sel.test_hook(kselect.KTH_HOOK_FAULT_BARRIER, 2)
+    try:
+        n = (1 << 23) + 13
+        keys, srt = _keys(gpu, n, "uniform_half")
+        assert sel.select(keys, n // 2) == srt[n // 2 - 1]  # times out once, redone per level
+        assert not sel.coop()
+        host = keys.cpu().numpy()
+        for largest in (False, True):
+            order = -host.astype(np.int64) if largest else host.astype(np.int64)
+            ranked = np.argsort(order, kind="stable")
+            for k in (100, n // 32, n // 4):  # k_main<1/2>, <5/6>, <3/4>
+                vals = torch.empty(k, dtype=torch.int32, device="cuda")
+                idx = torch.empty(k, dtype=torch.int64, device="cuda")
+                sel.topk(keys, n, k, vals, idx, largest=largest)
+                sel.sync()
+                assert not sel.coop(), (k, largest)
+                want = np.sort(ranked[:k])
+                np.testing.assert_array_equal(idx.cpu().numpy(), want, err_msg=f"k={k} {largest}")
+                np.testing.assert_array_equal(vals.cpu().numpy(), host[want], err_msg=f"k={k} {largest}")
+                assert sel.stats()["error"] == 0, (k, largest)
+        with _world1():
+            ds = DistSelector(HipBackend(0, sel))
+            for k in (1, n // 2, n):
+                got = int(ds.select(keys, n, n, k).item())
+                assert got == srt[k - 1], (k, sel.stats())
+                assert not sel.coop(), k
+            ds.close()
     finally:
         sel.close()
 
