@@ -122,6 +122,56 @@ int kth_select_f32_async(kth_ctx *ctx, const float *d_keys, int64_t n, int64_t k
 uint32_t kth_f32_order_key(float x);
 float kth_f32_of_order_key(uint32_t key);
 
+/* --- several ranks of one array ----------------------------------------------
+ * out[i] = the ks[i]-th smallest of keys[0..n), for m ranks at once: the
+ * quantiles of one array (numpy.partition(a, [k1, k2, ...])[[k1, k2, ...]]).
+ * ks is a host array of m 1-based ranks, read before the call returns; any
+ * order, duplicates allowed (a duplicate is resolved once and copied).  Every
+ * out[i] is bit-identical to what kth_select_i32 / kth_select_f32 returns for
+ * that rank; float32 keys follow kth_select_f32's order, NaN rule and
+ * canonical NaN.  The input is not modified.
+ *   1 <= m <= KTH_MULTI_MAX_RANKS and 1 <= ks[i] <= n, else KTH_EINVAL before
+ *   any device work with out untouched; KTH_ENODEV without a GPU.
+ * The forms are those of the single select: the one-shot and _ctx forms take
+ * host or device keys and are synchronous; the _async form takes device
+ * memory only, enqueues on the ctx stream, makes no host synchronisation, and
+ * no allocation once kth_ctx_reserve_multi(ctx, n, m) or an earlier call of
+ * the same size has sized the scratch (graph-capturable, as
+ * kth_select_i32_async).
+ * One pass: for n > 4 Mi keys on a ctx that runs the cooperative kernels, the
+ * call reads the input from HBM ONCE: a sample phase per distinct rank, one
+ * streaming launch that serves every rank's window from each loaded tile, a
+ * finish phase per distinct rank over that rank's own counts and candidates
+ * (with the single select's exact whole-input fallback for a rank whose
+ * window missed or overflowed; the other ranks are not disturbed).
+ * Not one pass, but exact: n <= 4 Mi keys (the LDS and radix paths), and a
+ * ctx on the per-level path (KTH_COOP=0, or backing off after a grid-barrier
+ * timeout); there the distinct ranks run one after the other through the
+ * single select.  A call with one distinct rank is the single select too.
+ * Scratch: beside the single select's, one candidate buffer per rank of
+ * kth_dist_cand_capacity(n) keys (2^30 keys, 8 ranks: 8 x 128 MiB = 1 GiB),
+ * and ~1.6 MB of slots.
+ * Errors: a device-side error on rank i shows in kth_ctx_multi_stats(ctx, i)
+ * .error; the synchronous forms then return KTH_EINTERNAL, and after a
+ * reported grid-barrier timeout they redo the call on the per-level path, as
+ * kth_select_i32_ctx does.  A multi call counts as one selection for the
+ * cooperative back-off.  kth_ctx_last_stats after a multi call returns rank
+ * m-1's stats.  Timing: on the one-pass path kth_ctx_take_timing counts a
+ * multi call as one select whose main_ms covers the one streaming launch. */
+#define KTH_MULTI_MAX_RANKS 8
+int kth_select_multi_i32(const int32_t *keys, int64_t n, const int64_t *ks, int m, int32_t *out);
+int kth_select_multi_i32_ctx(kth_ctx *ctx, const int32_t *keys, int64_t n, const int64_t *ks, int m, int32_t *out);
+int kth_select_multi_i32_async(kth_ctx *ctx, const int32_t *d_keys, int64_t n, const int64_t *ks, int m,
+                               int32_t *d_out);
+int kth_select_multi_f32(const float *keys, int64_t n, const int64_t *ks, int m, float *out);
+int kth_select_multi_f32_ctx(kth_ctx *ctx, const float *keys, int64_t n, const int64_t *ks, int m, float *out);
+int kth_select_multi_f32_async(kth_ctx *ctx, const float *d_keys, int64_t n, const int64_t *ks, int m, float *d_out);
+/* Pre-size the scratch of multi calls of up to m ranks over up to n keys. */
+int kth_ctx_reserve_multi(kth_ctx *ctx, int64_t n, int m);
+/* Stats of rank i (0 <= i < m) of the last multi call on this ctx
+ * (synchronises the ctx stream). */
+int kth_ctx_multi_stats(kth_ctx *ctx, int i, kth_stats *st);
+
 /* Stats of the last select on this ctx (synchronises the ctx stream). */
 int kth_ctx_last_stats(kth_ctx *ctx, kth_stats *st);
 

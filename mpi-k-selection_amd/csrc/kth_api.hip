@@ -73,6 +73,13 @@ constexpr u64 TK_STAGE_MAX_FRAC = 16;  // staged top-k (k_main<5/6>) for k <= n 
 constexpr int TK5_SPLIT = 4;            // workgroups per k_main workgroup in k_tk5_count / k_tk5_write (window-parallel)
 constexpr int COOP_BACKOFF = 64;        // synchronous selects on the per-level path after a grid-barrier timeout
 constexpr uint64_t DSCAN_PER_WG = 1ull << 16;  // candidates per workgroup of the sharded scan's first-digit histogram
+// A rank's set of a multi-rank call (kth_select_multi_*), in one allocation:
+// its three slots and candidate count, laid out as the ctx's islots, then its
+// own sample-phase slots (its k_finish clears them, as the ctx's)
+constexpr size_t MSET_HSLOT_OFF = ISLOT_WORDS;
+constexpr size_t MSET_WORDS = MSET_HSLOT_OFF + HSLOT_WORDS;
+static_assert(KTH_MULTI_MAX_RANKS == kth::MULTI_MAX, "include/kth.h rank limit");
+constexpr int MULTI_VARIANTS = 3;  // k_main_multi<2 / 4 / 8>
 
 #define HIP_TRY(x)                                                                                    \
     do {                                                                                              \
@@ -126,6 +133,7 @@ struct kth_ctx {
     // streaming-pass workgroups per k_main<TF, F32> variant, [key kind][TF]
     // (float32 keys have no TF 5 / 6: those entries stay 0)
     int main_grid[2][7] = {};
+    int multi_grid[2][MULTI_VARIANTS] = {};  // ... per k_main_multi<2 / 4 / 8, F32>, [key kind][variant]
     int main_wg_per_cu = 0;  // KTH_MAIN_WG_PER_CU: k_main workgroups a CU for every variant (0 = from its registers and LDS)
     bool fault_topk_rank = false;  // KTH_HOOK_FAULT_TOPK_RANK (tests): top-k selects a wrong rank on purpose
     bool fault_barrier = false;    // KTH_HOOK_FAULT_BARRIER (tests): the grid barriers report a timeout
@@ -164,6 +172,16 @@ struct kth_ctx {
     int32_t *h_status = nullptr;  // pinned
     SelState *h_state = nullptr;  // pinned
     int last_state = -1;
+    // multi-rank calls: a set per rank (states, slots, candidates), [answer, error] per rank
+    DevBuf<SelState> mstate;  // 2 per rank
+    DevBuf<u64> mslots;       // MSET_WORDS per rank, zero between calls
+    DevBuf<uint32_t> mcand;   // per rank: the candidates, mcand_stride words apart
+    int32_t *d_mstatus = nullptr, *h_mstatus = nullptr;  // 2 words per rank (device / pinned)
+    int multi_m = 0;          // ranks of the last multi call (0: none yet)
+    int multi_set[KTH_MULTI_MAX_RANKS] = {};  // ... and the set that resolved each (duplicates share one)
+    u64 multi_cap = 0;        // ... and its per-rank candidate capacity
+    bool multi_last = false;  // the last selection on this ctx was a multi call (kth_ctx_last_stats: its last rank)
+    bool multi_dirty = false; // a multi call was cut short or failed: re-zero mslots
     bool last_f32 = false;    // the last select's keys were float32 (kth_stats.answer: its bits)
     // timing: event pairs around the streaming pass and around whole selects
     bool timing = false;
@@ -315,20 +333,34 @@ void dump_stamps(kth_ctx *c) {
     c->stamp_next = 0;
 }
 
-StepArgs step(kth_ctx *c, int adv, int st_in, int st_out, const u64 *in, u64 *acc, u64 *zero) {
+// What one rank's selection owns beside its histogram slots: the two states
+// and the candidates.  The ctx's own set serves every single select; a
+// multi-rank call has one set per rank.
+struct RankSet {
+    SelState *st;     // 2 states (ping-pong)
+    u64 *cand_count;
+    uint32_t *cand;
+    u64 cap;          // candidate buffer capacity (keys)
+};
+RankSet own_set(kth_ctx *c) { return RankSet{c->st, cand_count(c), c->cand.p, c->cand.count}; }
+
+StepArgs step(kth_ctx *c, const RankSet &r, int adv, int st_in, int st_out, const u64 *in, u64 *acc, u64 *zero) {
     StepArgs a;
     memset(&a, 0, sizeof a);
     a.stamps = next_stamps(c);
-    a.st_in = st_in >= 0 ? c->st + st_in : nullptr;
-    a.st_out = c->st + st_out;
+    a.st_in = st_in >= 0 ? r.st + st_in : nullptr;
+    a.st_out = r.st + st_out;
     a.stats_in = in;
     a.stats_acc = acc;
     a.stats_zero = zero;
     a.adv = adv;
-    a.cand = c->cand.p;
-    a.cand_count = cand_count(c);
-    a.cap = c->cand.count;
+    a.cand = r.cand;
+    a.cand_count = r.cand_count;
+    a.cap = r.cap;
     return a;
+}
+StepArgs step(kth_ctx *c, int adv, int st_in, int st_out, const u64 *in, u64 *acc, u64 *zero) {
+    return step(c, own_set(c), adv, st_in, st_out, in, acc, zero);
 }
 
 // A chain of level steps over three rotating histogram slots and the two
@@ -342,13 +374,14 @@ StepArgs step(kth_ctx *c, int adv, int st_in, int st_out, const u64 *in, u64 *ac
 struct Chain {
     enum : unsigned { NONE = 0, IN = 1, ACC = 2, ZERO = 4, ALL = IN | ACC | ZERO };
     kth_ctx *c;
-    u64 *slots;  // the three slots: c->islots, or the sharded protocol's c->uslots
+    u64 *slots;  // the three slots: c->islots, the sharded protocol's c->uslots, or a multi-rank set's
     int l = 0;   // the next step
+    const RankSet *set = nullptr;  // the states and candidates (null: the ctx's own)
 
     u64 *slot(int i) const { return slots + (size_t)(i % 3) * kth::STATS_WORDS; }
     StepArgs next(int adv, unsigned use = ALL) {
         const bool init = adv == kth::ADV_INIT_SAMPLE || adv == kth::ADV_INIT_FULL;
-        StepArgs a = step(c, adv, init ? -1 : (l + 1) % 2, l % 2, use & IN ? slot(l) : nullptr,
+        StepArgs a = step(c, set ? *set : own_set(c), adv, init ? -1 : (l + 1) % 2, l % 2, use & IN ? slot(l) : nullptr,
                           use & ACC ? slot(l + 1) : nullptr, use & ZERO ? slot(l + 2) : nullptr);
         ++l;
         return a;
@@ -454,13 +487,15 @@ uint32_t *pre_set(kth_ctx *c, int set) {
 
 // with_pre: this select's k_main<0> histogrammed the candidates' first digit
 // into PreHist set fin_set
+// head_slots: the sample phase's slots this launch clears (null: the ctx's own)
 template <bool F32>
-void launch_finish(kth_ctx *c, StepArgs a, int32_t *d_out, int32_t *d_status, bool with_pre = false) {
+void launch_finish(kth_ctx *c, StepArgs a, int32_t *d_out, int32_t *d_status, bool with_pre = false,
+                   u64 *head_slots = nullptr) {
     const size_t mine = FSLOT_OFF + (size_t)c->fin_set * FSLOT_WORDS;
     a.stats_zero = c->islots + FSLOT_OFF + (size_t)(1 - c->fin_set) * FSLOT_WORDS;
     a.zero_words = FSLOT_WORDS;
     kth::CoopArgs x = coop_args(c, mine, d_out, d_status);
-    x.zero2 = c->islots + HSLOT_OFF;
+    x.zero2 = head_slots ? head_slots : c->islots + HSLOT_OFF;
     x.zero2_words = HSLOT_WORDS;
     x.pre = with_pre ? pre_set(c, c->fin_set) : nullptr;
     x.pre_zero = pre_set(c, 1 - c->fin_set);
@@ -630,13 +665,13 @@ void coop_tick(kth_ctx *c) {
     if (c->coop_backoff > 0 && --c->coop_backoff == 0) c->coop = c->coop_wanted;
 }
 
+// One select's launches; select_async below is the entry (it counts the
+// selection for the cooperative back-off, a multi-rank call counts once).
 template <bool F32 = false>
-int select_async(kth_ctx *c, const int32_t *d_keys, int64_t n, int64_t k, int32_t *d_out, int32_t *d_status,
-                 int tflag = 0, uint32_t *tflags = nullptr) {
-    if (!c || !d_keys || (!d_out && !d_status) || n < 1 || k < 1 || k > n) return KTH_EINVAL;
-    KTH_TRY(set_device(c));
-    coop_tick(c);
+int select_enqueue(kth_ctx *c, const int32_t *d_keys, int64_t n, int64_t k, int32_t *d_out, int32_t *d_status,
+                   int tflag = 0, uint32_t *tflags = nullptr) {
     c->last_f32 = F32;
+    c->multi_last = false;
     if (c->dirty) {
         HIP_TRY(hipMemsetAsync(c->islots, 0, SLOT_ALLOC_WORDS * sizeof(u64), c->stream));
         c->dirty = false;
@@ -653,6 +688,15 @@ int select_async(kth_ctx *c, const int32_t *d_keys, int64_t n, int64_t k, int32_
     if (rc != KTH_OK) c->dirty = true;
     if (c->stamps) dump_stamps(c);
     return rc;
+}
+
+template <bool F32 = false>
+int select_async(kth_ctx *c, const int32_t *d_keys, int64_t n, int64_t k, int32_t *d_out, int32_t *d_status,
+                 int tflag = 0, uint32_t *tflags = nullptr) {
+    if (!c || !d_keys || (!d_out && !d_status) || n < 1 || k < 1 || k > n) return KTH_EINVAL;
+    KTH_TRY(set_device(c));
+    coop_tick(c);
+    return select_enqueue<F32>(c, d_keys, n, k, d_out, d_status, tflag, tflags);
 }
 
 bool is_device_ptr(const void *p) {
@@ -767,10 +811,19 @@ std::array<const void *, 7> main_fns() {
 // holds 512 / alloc(VGPR) waves, MI355X_MICROARCH.md register files);
 // the top-k variants keep more keys live and may allocate more VGPRs.
 // hipOccupancyMaxActiveBlocksPerMultiprocessor under-reports here.
+template <bool F32>
+std::array<const void *, 7 + MULTI_VARIANTS> pass_fns() {
+    const std::array<const void *, 7> f = main_fns<F32>();
+    return {f[0], f[1], f[2], f[3], f[4], f[5], f[6],
+            reinterpret_cast<const void *>(kth::k_main_multi<2, F32>),
+            reinterpret_cast<const void *>(kth::k_main_multi<4, F32>),
+            reinterpret_cast<const void *>(kth::k_main_multi<8, F32>)};
+}
 void size_main_grids(kth_ctx *c) {
-    const std::array<const void *, 7> fns[2] = {main_fns<false>(), main_fns<true>()};  // [key kind][TF], as c->main_grid
+    // [key kind][TF] as c->main_grid, then the multi-rank variants as c->multi_grid
+    const std::array<const void *, 7 + MULTI_VARIANTS> fns[2] = {pass_fns<false>(), pass_fns<true>()};
     for (int kind = 0; kind < 2; ++kind)
-        for (int tf = 0; tf < 7; ++tf) {
+        for (int tf = 0; tf < 7 + MULTI_VARIANTS; ++tf) {
             if (!fns[kind][tf]) continue;
             int per = 4;
             hipFuncAttributes fa;
@@ -783,7 +836,7 @@ void size_main_grids(kth_ctx *c) {
             }
             (void)hipGetLastError();
             if (c->main_wg_per_cu > 0) per = c->main_wg_per_cu;
-            c->main_grid[kind][tf] = c->num_cu * per;
+            (tf < 7 ? c->main_grid[kind][tf] : c->multi_grid[kind][tf - 7]) = c->num_cu * per;
         }
 }
 
@@ -949,7 +1002,9 @@ int kth_ctx_destroy(kth_ctx *c) {
     if (c->st) (void)hipFree(c->st);
     if (c->islots) (void)hipFree(c->islots);
     release_all(c->sample, c->cand, c->cand_rows, c->tk_segv, c->tk_segp, c->tk_wcnt, c->tk_wstart, c->staging,
-                c->topk);
+                c->topk, c->mstate, c->mslots, c->mcand);
+    if (c->d_mstatus) (void)hipFree(c->d_mstatus);
+    if (c->h_mstatus) (void)hipHostFree(c->h_mstatus);
     if (c->d_status) (void)hipFree(c->d_status);
     if (c->stamps) (void)hipFree(c->stamps);
     if (c->h_status) (void)hipHostFree(c->h_status);
@@ -1048,19 +1103,254 @@ int select_ctx(kth_ctx *c, const int32_t *keys, int64_t n, int64_t k, int32_t *o
     return KTH_OK;
 }
 
+// The one-shot entry points' ctx: created on first use, one per host thread.
+int thread_ctx() {
+    if (tl_ctx) return KTH_OK;
+    int dev = 0;
+    if (kth_device_count() <= 0) return KTH_ENODEV;
+    if (hipGetDevice(&dev) != hipSuccess) {
+        (void)hipGetLastError();
+        dev = 0;
+    }
+    return kth_ctx_create(dev, &tl_ctx);
+}
+
 template <bool F32>
 int select_oneshot(const int32_t *keys, int64_t n, int64_t k, int32_t *out) {
     if (!keys || !out || n < 1 || k < 1 || k > n) return KTH_EINVAL;
-    if (!tl_ctx) {
-        int dev = 0;
-        if (kth_device_count() <= 0) return KTH_ENODEV;
-        if (hipGetDevice(&dev) != hipSuccess) {
-            (void)hipGetLastError();
-            dev = 0;
-        }
-        KTH_TRY(kth_ctx_create(dev, &tl_ctx));
-    }
+    KTH_TRY(thread_ctx());
     return select_ctx<F32>(tl_ctx, keys, n, k, out);
+}
+
+// ------------------------------------------------ several ranks of one array
+// kth_select_multi_*: up to KTH_MULTI_MAX_RANKS ranks of the same keys.  On
+// the window path with the cooperative kernels: k_head per distinct rank (each
+// into its own set), ONE k_main_multi over the input, k_finish per distinct
+// rank.  Otherwise (n <= RADIX_MAX_N, the per-level path, or one distinct
+// rank) the distinct ranks go one after the other through the single select's
+// launches, and each one's final state is copied into its set for
+// kth_ctx_multi_stats.
+bool multi_args_ok(const void *keys, int64_t n, const int64_t *ks, int m, const void *out) {
+    if (!keys || !ks || !out || n < 1 || m < 1 || m > KTH_MULTI_MAX_RANKS) return false;
+    for (int i = 0; i < m; ++i)
+        if (ks[i] < 1 || ks[i] > n) return false;
+    return true;
+}
+
+// candidate buffers of a multi call lie this many words apart (256-byte
+// aligned, so that k_finish reads each with 16-byte loads)
+u64 multi_stride(u64 cap) { return (cap + 63) & ~(u64)63; }
+
+// Scratch of a multi call of m ranks over n keys: the sets (states, slots,
+// status words: fixed size, made once) and, for the window path, m candidate
+// buffers of the single select's capacity each (at 2^30 keys: 2^25 keys = 128
+// MiB a rank, 1 GiB for eight) beside the single select's own scratch, which
+// the per-level path uses.
+int reserve_multi(kth_ctx *c, int64_t n, int m) {
+    if (c->mslots.count == 0) {
+        KTH_TRY(c->mstate.reserve(2 * (u64)KTH_MULTI_MAX_RANKS));
+        KTH_TRY(c->mslots.reserve((u64)KTH_MULTI_MAX_RANKS * MSET_WORDS));
+        HIP_TRY(hipMemsetAsync(c->mstate.p, 0, c->mstate.count * sizeof(SelState), c->stream));
+        HIP_TRY(hipMemsetAsync(c->mslots.p, 0, c->mslots.count * sizeof(u64), c->stream));
+    }
+    if (!c->d_mstatus && hipMalloc(reinterpret_cast<void **>(&c->d_mstatus), 2 * KTH_MULTI_MAX_RANKS * sizeof(int32_t)) != hipSuccess) {
+        (void)hipGetLastError();
+        c->d_mstatus = nullptr;
+        return KTH_ENOMEM;
+    }
+    if (!c->h_mstatus && hipHostMalloc(reinterpret_cast<void **>(&c->h_mstatus), 2 * KTH_MULTI_MAX_RANKS * sizeof(int32_t), 0) != hipSuccess) {
+        (void)hipGetLastError();
+        c->h_mstatus = nullptr;
+        return KTH_ENOMEM;
+    }
+    if (n <= RADIX_MAX_N) return KTH_OK;
+    KTH_TRY(reserve_window(c, n));
+    return c->mcand.reserve((u64)m * multi_stride(cand_capacity(n)));
+}
+
+template <bool F32>
+void launch_main_multi(kth_ctx *c, const kth::MultiArgs &ma) {
+    const int v = ma.m <= 2 ? 0 : ma.m <= 4 ? 1 : 2;  // as c->multi_grid
+    const int g = c->multi_grid[F32][v];
+    switch (v) {
+    case 0: kth::k_main_multi<2, F32><<<g, kth::BLK, 0, c->stream>>>(ma); break;
+    case 1: kth::k_main_multi<4, F32><<<g, kth::BLK, 0, c->stream>>>(ma); break;
+    default: kth::k_main_multi<8, F32><<<g, kth::BLK, 0, c->stream>>>(ma); break;
+    }
+}
+
+// The one-pass path over D distinct ranks: rank j's answer to outs[j] (device,
+// may be null) and its [answer, error] to d_status + 2 j (may be null).  Each
+// rank's chain is run_window's cooperative one over its own set; the ctx's
+// k_finish slot sets, barrier words and tail buffer serve the launches in
+// turn (they are stream-ordered).
+template <bool F32>
+int run_multi_window(kth_ctx *c, const int32_t *keys, int64_t n, const int64_t *ks, int D, int32_t *const *outs,
+                     int32_t *d_status) {
+    const int64_t s = sample_size(n);
+    const u64 nchunks = ((u64)s + kth::SAMPLE_CHUNK - 1) / kth::SAMPLE_CHUNK;
+    const u64 stride = (u64)n / nchunks;
+    const u64 cap = cand_capacity(n), cstride = multi_stride(cap);
+    RankSet sets[KTH_MULTI_MAX_RANKS];
+    Chain chains[KTH_MULTI_MAX_RANKS] = {};
+    u64 *head_slots[KTH_MULTI_MAX_RANKS];
+    kth::MultiArgs ma;
+    memset(&ma, 0, sizeof ma);
+    ma.keys = keys;
+    ma.n = (u64)n;
+    ma.m = D;
+    for (int j = 0; j < D; ++j) {
+        u64 *slots = c->mslots.p + (size_t)j * MSET_WORDS;
+        head_slots[j] = slots + MSET_HSLOT_OFF;
+        sets[j] = RankSet{c->mstate.p + 2 * (size_t)j, slots + 3 * (size_t)kth::STATS_WORDS,
+                          c->mcand.p + (size_t)j * cstride, cap};
+        // sample phase -> this rank's window in state 0 of its set (the
+        // single select's window: the same early-window floor)
+        Chain ch{c, slots, 2, &sets[j]};
+        u64 r_lo, r_hi;
+        window_ranks(n, ks[j], s, &r_lo, &r_hi);
+        StepArgs a = head_step(ch, n, ks[j], s, r_lo, r_hi, true);
+        kth::CoopArgs hx = coop_args(c, 0, nullptr, nullptr);
+        hx.slots = head_slots[j];
+        if (c->head_abs_div) hx.abs_min = (u64)s / c->head_abs_div;
+        kth::k_head<F32><<<gather_grid(nchunks), kth::DENSE_BLK, 0, c->stream>>>(a, hx, keys, (u64)n, stride,
+                                                                               c->sample.p, (u64)s);
+        a = ch.next(kth::ADV_CARRY, Chain::ACC);
+        ma.w[j] = kth::MultiWin{a.st_in, a.st_out, a.stats_acc, a.cand_count, sets[j].cand, a.cap};
+        chains[j] = ch;
+    }
+    ev_main(c);
+    launch_main_multi<F32>(c, ma);
+    ev_main(c);
+    for (int j = 0; j < D; ++j) {
+        StepArgs a = chains[j].next(kth::ADV_DECIDE, Chain::IN);
+        over_keys(a, keys, n);
+        launch_finish<F32>(c, a, outs[j], d_status ? d_status + 2 * j : nullptr, false, head_slots[j]);
+    }
+    return launch_check();
+}
+
+// d_out: m answers on the device, or null; status: also [answer, error] per
+// distinct rank into c->d_mstatus (set j = c->multi_set[i] resolved rank i).
+template <bool F32>
+int multi_async(kth_ctx *c, const int32_t *d_keys, int64_t n, const int64_t *ks, int m, int32_t *d_out, bool status) {
+    KTH_TRY(set_device(c));
+    coop_tick(c);  // one selection, however many ranks
+    int64_t dk[KTH_MULTI_MAX_RANKS];
+    int first[KTH_MULTI_MAX_RANKS], D = 0;
+    for (int i = 0; i < m; ++i) {  // duplicate ranks are resolved once
+        int j = 0;
+        while (j < D && dk[j] != ks[i]) ++j;
+        if (j == D) {
+            dk[D] = ks[i];
+            first[D++] = i;
+        }
+        c->multi_set[i] = j;
+    }
+    c->multi_m = m;
+    KTH_TRY(reserve_multi(c, n, D));
+    int32_t *outs[KTH_MULTI_MAX_RANKS];
+    for (int j = 0; j < D; ++j) outs[j] = d_out ? d_out + first[j] : nullptr;
+    int32_t *d_status = status ? c->d_mstatus : nullptr;
+    int rc = KTH_OK;
+    // (one distinct rank is the single select: k_main<0> alone is HBM-bound,
+    // 0.70 against 0.78 ms at 2^30 through k_main_multi)
+    if (n > RADIX_MAX_N && c->coop && D > 1) {
+        if (c->dirty) {
+            HIP_TRY(hipMemsetAsync(c->islots, 0, SLOT_ALLOC_WORDS * sizeof(u64), c->stream));
+            c->dirty = false;
+        }
+        if (c->multi_dirty) {
+            HIP_TRY(hipMemsetAsync(c->mslots.p, 0, c->mslots.count * sizeof(u64), c->stream));
+            c->multi_dirty = false;
+        }
+        c->last_f32 = F32;
+        c->multi_cap = cand_capacity(n);
+        ev_mark(c, c->ev_total, c->total_used);
+        rc = run_multi_window<F32>(c, d_keys, n, dk, D, outs, d_status);
+        ev_mark(c, c->ev_total, c->total_used);
+        if (c->stamps) dump_stamps(c);
+    } else {
+        for (int j = 0; j < D && rc == KTH_OK; ++j) {
+            rc = select_enqueue<F32>(c, d_keys, n, dk[j], outs[j], d_status ? d_status + 2 * j : nullptr);
+            if (rc == KTH_OK && hipMemcpyAsync(c->mstate.p + 2 * (size_t)j, c->st + c->last_state, sizeof(SelState),
+                                               hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
+                rc = KTH_EHIP;
+        }
+        c->multi_cap = c->cand.count;
+    }
+    if (rc != KTH_OK) {
+        c->dirty = c->multi_dirty = true;
+        return rc;
+    }
+    if (d_out)
+        for (int i = 0; i < m; ++i)
+            if (first[c->multi_set[i]] != i)
+                HIP_TRY(hipMemcpyAsync(d_out + i, d_out + first[c->multi_set[i]], sizeof(int32_t),
+                                       hipMemcpyDeviceToDevice, c->stream));
+    c->multi_last = true;
+    return KTH_OK;
+}
+
+// One multi call with its status words fetched into h_mstatus.
+template <bool F32>
+int multi_fetch(kth_ctx *c, const int32_t *dk, int64_t n, const int64_t *ks, int m) {
+    KTH_TRY(multi_async<F32>(c, dk, n, ks, m, nullptr, true));
+    HIP_TRY(hipMemcpyAsync(c->h_mstatus, c->d_mstatus, 2 * KTH_MULTI_MAX_RANKS * sizeof(int32_t), hipMemcpyDeviceToHost,
+                           c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return KTH_OK;
+}
+
+// The synchronous multi call through a ctx, either key kind (as select_ctx).
+template <bool F32>
+int multi_ctx(kth_ctx *c, const int32_t *keys, int64_t n, const int64_t *ks, int m, int32_t *out) {
+    if (!c || !multi_args_ok(keys, n, ks, m, out)) return KTH_EINVAL;
+    KTH_TRY(set_device(c));
+    const int32_t *dk = keys;
+    if (!is_device_ptr(keys)) {
+        KTH_TRY(c->staging.reserve((u64)n));
+        HIP_TRY(hipMemcpyAsync(c->staging.p, keys, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        dk = c->staging.p;
+    }
+    KTH_TRY(multi_fetch<F32>(c, dk, n, ks, m));
+    auto any_error = [&](bool barrier_only) {
+        for (int i = 0; i < m; ++i) {
+            const int32_t e = c->h_mstatus[2 * c->multi_set[i] + 1];
+            if (barrier_only ? e == (int32_t)kth::ERR_BARRIER : e != 0) return true;
+        }
+        return false;
+    };
+    if (c->coop && any_error(true)) {
+        // a cooperative grid was not co-resident: redo every rank on the
+        // per-level path and stay on it, as select_ctx does
+        c->dirty = c->multi_dirty = true;
+        c->coop = false;
+        c->coop_backoff = COOP_BACKOFF + 1;  // (the retry below counts one)
+        KTH_TRY(multi_fetch<F32>(c, dk, n, ks, m));
+    }
+    if (any_error(false)) {
+        c->dirty = c->multi_dirty = true;
+        return KTH_EINTERNAL;
+    }
+    for (int i = 0; i < m; ++i) {
+        const int32_t w = c->h_mstatus[2 * c->multi_set[i]];
+        out[i] = F32 ? (int32_t)kth::f32_of_key((uint32_t)w ^ 0x80000000u) : w;
+    }
+    return KTH_OK;
+}
+
+template <bool F32>
+int multi_oneshot(const int32_t *keys, int64_t n, const int64_t *ks, int m, int32_t *out) {
+    if (!multi_args_ok(keys, n, ks, m, out)) return KTH_EINVAL;
+    KTH_TRY(thread_ctx());
+    return multi_ctx<F32>(tl_ctx, keys, n, ks, m, out);
+}
+
+template <bool F32>
+int multi_entry_async(kth_ctx *c, const int32_t *d_keys, int64_t n, const int64_t *ks, int m, int32_t *d_out) {
+    if (!c || !multi_args_ok(d_keys, n, ks, m, d_out)) return KTH_EINVAL;
+    return multi_async<F32>(c, d_keys, n, ks, m, d_out, false);
 }
 
 }  // namespace
@@ -1083,6 +1373,32 @@ int kth_select_f32(const float *keys, int64_t n, int64_t k, float *out) {
     return select_oneshot<true>(reinterpret_cast<const int32_t *>(keys), n, k, reinterpret_cast<int32_t *>(out));
 }
 
+int kth_select_multi_i32(const int32_t *keys, int64_t n, const int64_t *ks, int m, int32_t *out) {
+    return multi_oneshot<false>(keys, n, ks, m, out);
+}
+int kth_select_multi_i32_ctx(kth_ctx *c, const int32_t *keys, int64_t n, const int64_t *ks, int m, int32_t *out) {
+    return multi_ctx<false>(c, keys, n, ks, m, out);
+}
+int kth_select_multi_i32_async(kth_ctx *c, const int32_t *d_keys, int64_t n, const int64_t *ks, int m,
+                               int32_t *d_out) {
+    return multi_entry_async<false>(c, d_keys, n, ks, m, d_out);
+}
+int kth_select_multi_f32(const float *keys, int64_t n, const int64_t *ks, int m, float *out) {
+    return multi_oneshot<true>(reinterpret_cast<const int32_t *>(keys), n, ks, m, reinterpret_cast<int32_t *>(out));
+}
+int kth_select_multi_f32_ctx(kth_ctx *c, const float *keys, int64_t n, const int64_t *ks, int m, float *out) {
+    return multi_ctx<true>(c, reinterpret_cast<const int32_t *>(keys), n, ks, m, reinterpret_cast<int32_t *>(out));
+}
+int kth_select_multi_f32_async(kth_ctx *c, const float *d_keys, int64_t n, const int64_t *ks, int m, float *d_out) {
+    return multi_entry_async<true>(c, reinterpret_cast<const int32_t *>(d_keys), n, ks, m,
+                                   reinterpret_cast<int32_t *>(d_out));
+}
+int kth_ctx_reserve_multi(kth_ctx *c, int64_t n, int m) {
+    if (!c || n < 0 || m < 1 || m > KTH_MULTI_MAX_RANKS) return KTH_EINVAL;
+    KTH_TRY(set_device(c));
+    return reserve_multi(c, n, m);
+}
+
 uint32_t kth_f32_order_key(float x) {
     uint32_t b;
     memcpy(&b, &x, sizeof b);
@@ -1101,12 +1417,14 @@ int kth_ctx_coop(const kth_ctx *c) {
     return c->coop ? 1 : 0;
 }
 
-int kth_ctx_last_stats(kth_ctx *c, kth_stats *out) {
-    if (!c || !out) return KTH_EINVAL;
-    if (c->last_state < 0) return KTH_EINVAL;
+}  // extern "C"
+
+namespace {
+
+// A selection state on the device as kth_stats (synchronises the ctx stream).
+int fetch_stats(kth_ctx *c, const SelState *d_state, u64 capacity, kth_stats *out) {
     KTH_TRY(set_device(c));
-    HIP_TRY(hipMemcpyAsync(c->h_state, c->st + c->last_state, sizeof(SelState), hipMemcpyDeviceToHost,
-                           c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_state, d_state, sizeof(SelState), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     const SelState &s = *c->h_state;
     memset(out, 0, sizeof *out);
@@ -1120,10 +1438,29 @@ int kth_ctx_last_stats(kth_ctx *c, kth_stats *out) {
     out->cnt_eq_lo = s.cnt[kth::C_EQLO];
     out->cnt_eq_hi = s.cnt[kth::C_EQHI];
     out->candidates = s.cnt[kth::C_IN];
-    out->capacity = c->cand.count;
+    out->capacity = capacity;
     out->answer = c->last_f32 ? (int32_t)kth::f32_of_key(s.answer) : (int32_t)(s.answer ^ 0x80000000u);
     out->error = (int32_t)s.error;
     return KTH_OK;
+}
+
+// rank i of the last multi call: its final state is state 0 of its set
+int multi_stats(kth_ctx *c, int i, kth_stats *out) {
+    if (!c || !out || i < 0 || i >= c->multi_m) return KTH_EINVAL;
+    return fetch_stats(c, c->mstate.p + 2 * (size_t)c->multi_set[i], c->multi_cap, out);
+}
+
+}  // namespace
+
+extern "C" {
+
+int kth_ctx_multi_stats(kth_ctx *c, int i, kth_stats *out) { return multi_stats(c, i, out); }
+
+int kth_ctx_last_stats(kth_ctx *c, kth_stats *out) {
+    if (!c || !out) return KTH_EINVAL;
+    if (c->multi_last) return multi_stats(c, c->multi_m - 1, out);
+    if (c->last_state < 0) return KTH_EINVAL;
+    return fetch_stats(c, c->st + c->last_state, c->cand.count, out);
 }
 
 int kth_ctx_enable_timing(kth_ctx *c, int on) {
@@ -1569,6 +1906,7 @@ static int launch_dresult(kth_ctx *c, int L, int32_t *d_out, uint32_t early) {
                                                             ISLOT_WORDS + HSLOT_WORDS, early);
     c->last_state = L % 2;
     c->last_f32 = false;  // (the sharded protocol is int32 only)
+    c->multi_last = false;
     return launch_check();
 }
 

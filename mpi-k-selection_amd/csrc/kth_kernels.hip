@@ -2011,4 +2011,5 @@ __global__ __launch_bounds__(BLK) void k_state_bcast(const SelState *src, StateP
 }  // namespace kth
 
 #include "kth_coop.hpp"
+#include "kth_multi.hpp"
 #include "kth_rows.hpp"

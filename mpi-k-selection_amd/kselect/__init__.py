@@ -38,6 +38,7 @@ from ._lib import (  # noqa: F401
     KTH_HOOK_FAULT_BARRIER,
     KTH_HOOK_FAULT_TOPK_RANK,
     KTH_HOOK_TOPK_SEG_CAP,
+    KTH_MULTI_MAX_RANKS,
     KTH_OK,
     KTH_PATH_LDS,
     KTH_PATH_RADIX,
@@ -103,6 +104,25 @@ def _need_f32(x, what):
 def _f32_from_bits(bits):
     """np.float32 holding exactly these 32 bits (signed zeros, subnormals and the NaN kept)."""
     return np.array([bits & 0xFFFFFFFF], dtype=np.uint32).view(np.float32)[0]
+
+
+def _rank_groups(ks):
+    """The ranks as (offset, ctypes int64 array) groups of at most KTH_MULTI_MAX_RANKS."""
+    ks = [int(k) for k in ks]
+    if not ks:
+        raise ValueError("ks is empty")
+    for at in range(0, len(ks), KTH_MULTI_MAX_RANKS):
+        part = ks[at:at + KTH_MULTI_MAX_RANKS]
+        yield at, (ctypes.c_int64 * len(part))(*part)
+
+
+def _multi_host_keys(keys, f32):
+    """select_multi's keys: a host array in the call's dtype, a tensor checked with f32=True."""
+    if isinstance(keys, np.ndarray):
+        keys = np.ascontiguousarray(keys, dtype=np.float32 if f32 else np.int32)
+    if f32:
+        _need_f32(keys, "keys")
+    return keys
 
 
 def _stream_handle(stream):
@@ -191,6 +211,45 @@ class Selector:
         check(LIB.kth_select_i32_async(self._ctx, _ptr(d_keys), int(n), int(k), _ptr(d_out)),
               "kth_select_i32_async")
 
+    def select_multi(self, keys, ks, n=None, f32=False):
+        """The ks[i]-th smallest (1-based) of the keys for every rank in ks, in one
+        streaming pass per group of KTH_MULTI_MAX_RANKS ranks (kth_select_multi_*_ctx):
+        a numpy int32 array (f32=True: float32 with the answers' exact bits).  Keys
+        as Selector.select; any order of ranks, duplicates allowed."""
+        keys = _multi_host_keys(keys, f32)
+        if n is None:
+            n = _numel(keys)
+        fn, what = ((LIB.kth_select_multi_f32_ctx, "kth_select_multi_f32_ctx") if f32
+                    else (LIB.kth_select_multi_i32_ctx, "kth_select_multi_i32_ctx"))
+        groups = list(_rank_groups(ks))
+        out = np.empty(sum(len(g) for _, g in groups), dtype=np.float32 if f32 else np.int32)
+        for at, g in groups:
+            check(fn(self._ctx, _ptr(keys), int(n), g, len(g), out[at:].ctypes.data), what)
+        return out
+
+    def select_multi_async(self, d_keys, n, ks, d_out, f32=False):
+        """Enqueue the selection of every rank in ks over device keys; answer i lands
+        in device int32 d_out[i] (f32=True: float32 keys, float32 d_out).  d_out holds
+        len(ks) contiguous elements."""
+        if f32:
+            _need_f32(d_keys, "d_keys")
+            _need_f32(d_out, "d_out")
+        fn, what = ((LIB.kth_select_multi_f32_async, "kth_select_multi_f32_async") if f32
+                    else (LIB.kth_select_multi_i32_async, "kth_select_multi_i32_async"))
+        for at, g in _rank_groups(ks):
+            check(fn(self._ctx, _ptr(d_keys), int(n), g, len(g), _ptr(d_out) + 4 * at), what)
+
+    def reserve_multi(self, n, m):
+        """Pre-size the scratch of multi calls of m ranks (at most a group's
+        KTH_MULTI_MAX_RANKS at a time) over n keys."""
+        check(LIB.kth_ctx_reserve_multi(self._ctx, int(n), min(int(m), KTH_MULTI_MAX_RANKS)), "kth_ctx_reserve_multi")
+
+    def multi_stats(self, i):
+        """Stats of rank i of the last group of ranks sent (kth_ctx_multi_stats)."""
+        st = KthStats()
+        check(LIB.kth_ctx_multi_stats(self._ctx, int(i), ctypes.byref(st)), "kth_ctx_multi_stats")
+        return st.as_dict()
+
     def coop(self):
         """True while the ctx runs the cooperative grid-barrier kernels (kth_ctx_coop)."""
         r = LIB.kth_ctx_coop(self._ctx)
@@ -274,6 +333,19 @@ def kth_select(keys, k, f32=False):
     out = ctypes.c_int32()
     check(LIB.kth_select_i32(_ptr(keys), int(n), int(k), ctypes.byref(out)), "kth_select_i32")
     return out.value
+
+
+def kth_select_multi(keys, ks, f32=False):
+    """One-shot (data, n, ranks) -> values: kth_select_multi_i32 (f32=True:
+    kth_select_multi_f32), as Selector.select_multi."""
+    keys = _multi_host_keys(keys, f32)
+    fn, what = ((LIB.kth_select_multi_f32, "kth_select_multi_f32") if f32
+                else (LIB.kth_select_multi_i32, "kth_select_multi_i32"))
+    groups = list(_rank_groups(ks))
+    out = np.empty(sum(len(g) for _, g in groups), dtype=np.float32 if f32 else np.int32)
+    for at, g in groups:
+        check(fn(_ptr(keys), int(_numel(keys)), g, len(g), out[at:].ctypes.data), what)
+    return out
 
 
 class ShardedSelector:

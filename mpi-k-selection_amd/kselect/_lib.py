@@ -25,12 +25,14 @@ KTH_DIST_DONE = 3  # kth_dist_level: no collective left, call kth_dist_result
 KTH_DIST_MAX_LEVELS = 3
 KTH_ROWS_MAX_COLS = 16384
 KTH_TOPK_MAX_COLS = 4096
+KTH_MULTI_MAX_RANKS = 8
 # kth_ctx_test_hook (tests only): fault injectors, off in every new ctx
 KTH_HOOK_FAULT_TOPK_RANK, KTH_HOOK_FAULT_BARRIER, KTH_HOOK_TOPK_SEG_CAP = 1, 2, 3
 
 c_i32p = ctypes.POINTER(ctypes.c_int32)
 c_u32p = ctypes.POINTER(ctypes.c_uint32)
 c_u64p = ctypes.POINTER(ctypes.c_uint64)
+c_i64p = ctypes.POINTER(ctypes.c_int64)
 c_vp = ctypes.c_void_p
 
 
@@ -90,6 +92,14 @@ PROTOS = {
     "kth_select_f32": (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int64, c_vp]),
     "kth_select_f32_ctx": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, c_vp]),
     "kth_select_f32_async": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, c_vp]),
+    "kth_select_multi_i32": (ctypes.c_int, [c_vp, ctypes.c_int64, c_i64p, ctypes.c_int, c_vp]),
+    "kth_select_multi_i32_ctx": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_i64p, ctypes.c_int, c_vp]),
+    "kth_select_multi_i32_async": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_i64p, ctypes.c_int, c_vp]),
+    "kth_select_multi_f32": (ctypes.c_int, [c_vp, ctypes.c_int64, c_i64p, ctypes.c_int, c_vp]),
+    "kth_select_multi_f32_ctx": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_i64p, ctypes.c_int, c_vp]),
+    "kth_select_multi_f32_async": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_i64p, ctypes.c_int, c_vp]),
+    "kth_ctx_reserve_multi": (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int]),
+    "kth_ctx_multi_stats": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.POINTER(KthStats)]),
     "kth_f32_order_key": (ctypes.c_uint32, [ctypes.c_float]),
     "kth_f32_of_order_key": (ctypes.c_float, [ctypes.c_uint32]),
     "kth_ctx_last_stats": (ctypes.c_int, [c_vp, ctypes.POINTER(KthStats)]),
