@@ -51,6 +51,8 @@ extern "C" {
 #define KTH_PATH_RADIX 2    /* multi-pass radix select over the input                  */
 #define KTH_PATH_WINDOW 3   /* sample window + one streaming pass + candidate radix    */
 #define KTH_PATH_WINDOW_FALLBACK 4 /* window missed -> radix passes over the input     */
+#define KTH_PATH_K16 5      /* 16-bit keys: settled by the first streaming pass        */
+#define KTH_PATH_K16_FALLBACK 6 /* 16-bit keys: a second (or third) pass was taken     */
 
 typedef struct kth_ctx kth_ctx;
 
@@ -172,6 +174,61 @@ int kth_ctx_reserve_multi(kth_ctx *ctx, int64_t n, int m);
  * (synchronises the ctx stream). */
 int kth_ctx_multi_stats(kth_ctx *ctx, int i, kth_stats *st);
 
+/* --- 16-bit keys (one array) ---------------------------------------------------
+ * The select and the multi-rank select for int16, uint16, float16 and bfloat16
+ * keys, read as 2-byte words (a caller need not widen them to 32 bits).  kind
+ * names the order: */
+#define KTH_K16_I16  0   /* signed order                                   */
+#define KTH_K16_U16  1   /* unsigned order                                 */
+#define KTH_K16_F16  2   /* IEEE binary16, total order, NaN above +inf     */
+#define KTH_K16_BF16 3   /* bfloat16, same rule                            */
+/* kth_k16_order_key(bits, kind) is the uint16 whose unsigned order is the key
+ * order: i16 bits ^ 0x8000, u16 bits; f16 / bf16 the float32 rule at 16 bits
+ * (negative b -> ~b, any other b -> b | 0x8000, every NaN -> 0xFFFF; so -0.0 <
+ * +0.0, subnormals distinct, every NaN equal to every other and above +inf,
+ * whose keys are 0xFC00 / 0xFF80).  kth_k16_of_order_key is its inverse, 0xFFFF
+ * -> the canonical quiet NaN 0x7E00 / 0x7FC0.  An unknown kind gives 0 from
+ * both.  Host arithmetic, no device needed; the definitions the kernels
+ * compile (csrc/kth_k16.hpp).
+ * The selects follow kth_select_f32* and kth_select_multi_*: k and ks[i] are
+ * 1-based, 1 <= m <= KTH_MULTI_MAX_RANKS, ranks in any order, a duplicate is
+ * resolved once and copied; a bad n / k / m / kind / pointer is KTH_EINVAL
+ * before any device work with out untouched, no GPU is KTH_ENODEV; the input
+ * is not modified; the one-shot and _ctx forms take host or device keys and
+ * are synchronous (they read the status once: a device-side error is
+ * KTH_EINTERNAL); the _async forms take device memory only, enqueue on the ctx
+ * stream, never synchronise, and allocate nothing once
+ * kth_ctx_reserve_k16(ctx, n, m) or any earlier k16 call has run (the scratch,
+ * ~1.3 MB, does not depend on n or m), so they are graph-capturable.  The
+ * answer has the bit pattern of an input element, a NaN comes back canonical.
+ * d_keys needs only 2-byte alignment.  Counts and ranks are 64-bit.
+ * n <= 32768: the full 65536-bin histogram decides.  Above: a sample window
+ * per distinct rank and ONE streaming launch for all ranks read the input once;
+ * whether a second (and third) pass is needed is decided on the device, their
+ * launches are always enqueued and return at once when every rank is settled.
+ * Worst case: the input is read three times beside the sample.  The path has
+ * no cooperative launch and no grid barrier: kth_ctx_coop's state is neither
+ * used nor counted down.
+ * Stats: kth_ctx_last_stats after a single k16 select and kth_ctx_multi_stats
+ * (ctx, i) after a multi call give path KTH_PATH_K16 (one pass) or
+ * KTH_PATH_K16_FALLBACK, lo_key / hi_key the last pass's window as 16-bit order
+ * keys, cnt_lt the keys below it, candidates the keys inside, answer the
+ * answer's bits, error the device-side error word.  kth_ctx_take_timing counts
+ * a k16 call as one select whose main_ms is the first streaming launch (for
+ * n <= 32768, where there is none, the histogram launch).  After a fallback
+ * the window reported is the narrowed one of the last pass, not the sample's. */
+uint16_t kth_k16_order_key(uint16_t bits, int kind);
+uint16_t kth_k16_of_order_key(uint16_t key, int kind);
+int kth_select_k16(const void *keys, int64_t n, int64_t k, int kind, uint16_t *out); /* host or device keys */
+int kth_select_k16_ctx(kth_ctx *ctx, const void *keys, int64_t n, int64_t k, int kind, uint16_t *out);
+int kth_select_k16_async(kth_ctx *ctx, const void *d_keys, int64_t n, int64_t k, int kind, uint16_t *d_out);
+int kth_select_multi_k16(const void *keys, int64_t n, const int64_t *ks, int m, int kind, uint16_t *out);
+int kth_select_multi_k16_ctx(kth_ctx *ctx, const void *keys, int64_t n, const int64_t *ks, int m, int kind,
+                             uint16_t *out);
+int kth_select_multi_k16_async(kth_ctx *ctx, const void *d_keys, int64_t n, const int64_t *ks, int m, int kind,
+                               uint16_t *d_out);
+int kth_ctx_reserve_k16(kth_ctx *ctx, int64_t n, int m);
+
 /* Stats of the last select on this ctx (synchronises the ctx stream). */
 int kth_ctx_last_stats(kth_ctx *ctx, kth_stats *st);
 
@@ -192,10 +249,14 @@ int kth_ctx_coop(const kth_ctx *ctx);
  *                             launch does; 0: off
  *   KTH_HOOK_TOPK_SEG_CAP     entries per staged top-k segment (0 = sized from n;
  *                             small values force the segment-overflow fallback)
+ *   KTH_HOOK_K16_MISS         value != 0: the sample phase of the 16-bit select
+ *                             publishes a window that holds no key, so the
+ *                             later passes must produce every answer
  * Returns KTH_EINVAL for an unknown hook or a bad value. */
 #define KTH_HOOK_FAULT_TOPK_RANK 1
 #define KTH_HOOK_FAULT_BARRIER 2
 #define KTH_HOOK_TOPK_SEG_CAP 3
+#define KTH_HOOK_K16_MISS 4
 int kth_ctx_test_hook(kth_ctx *ctx, int hook, int64_t value);
 
 /* --- timing (bench) ----------------------------------------------------------

@@ -20,6 +20,7 @@
 #include "kth_internal.h"
 #include "kth_kernels.hip"
 #include "kth_topk.hpp"
+#include "kth_k16.hpp"
 
 using kth::SelState;
 using kth::StepArgs;
@@ -80,6 +81,12 @@ constexpr size_t MSET_HSLOT_OFF = ISLOT_WORDS;
 constexpr size_t MSET_WORDS = MSET_HSLOT_OFF + HSLOT_WORDS;
 static_assert(KTH_MULTI_MAX_RANKS == kth::MULTI_MAX, "include/kth.h rank limit");
 constexpr int MULTI_VARIANTS = 3;  // k_main_multi<2 / 4 / 8>
+// 16-bit keys (kth_k16.hpp): the sample histogram (u32 bins), then a set per rank
+constexpr size_t K16_SHIST_WORDS = kth::K16_VALUES / 2;  // (in u64 words)
+constexpr size_t K16_BUF_WORDS = K16_SHIST_WORDS + (size_t)KTH_MULTI_MAX_RANKS * kth::K16_RANK_WORDS;
+constexpr size_t K16_HIST_LDS = (size_t)kth::K16_VALUES * 2;
+static_assert(KTH_K16_I16 == 0 && KTH_K16_U16 == 1 && KTH_K16_F16 == 2 && KTH_K16_BF16 == 3, "kth_k16.hpp's key kinds");
+static_assert(KTH_PATH_K16 == 5 && KTH_PATH_K16_FALLBACK == 6, "kth_k16.hpp's paths");
 
 #define HIP_TRY(x)                                                                                    \
     do {                                                                                              \
@@ -183,6 +190,16 @@ struct kth_ctx {
     bool multi_last = false;  // the last selection on this ctx was a multi call (kth_ctx_last_stats: its last rank)
     bool multi_dirty = false; // a multi call was cut short or failed: re-zero mslots
     bool last_f32 = false;    // the last select's keys were float32 (kth_stats.answer: its bits)
+    // 16-bit keys: the sample histogram and the ranks' sets, their states; the
+    // call's rank -> set map and status words are the multi call's
+    DevBuf<u64> k16;
+    DevBuf<kth::K16State> k16st;
+    int k16_grid[3] = {};     // k16_main<0 / 1 / 2>'s workgroups
+    bool k16_ready = false;   // grids sized, k16_hist's LDS granted
+    bool k16_dirty = false;   // a k16 call was cut short or failed: re-zero its scratch
+    bool k16_miss = false;    // KTH_HOOK_K16_MISS (tests): the sample phase publishes an empty window
+    bool last_k16 = false;    // the last selection on this ctx had 16-bit keys
+    int k16_kind = 0;         // ... of this kind
     // timing: event pairs around the streaming pass and around whole selects
     bool timing = false;
     std::vector<hipEvent_t> ev_main, ev_total;
@@ -671,7 +688,7 @@ template <bool F32 = false>
 int select_enqueue(kth_ctx *c, const int32_t *d_keys, int64_t n, int64_t k, int32_t *d_out, int32_t *d_status,
                    int tflag = 0, uint32_t *tflags = nullptr) {
     c->last_f32 = F32;
-    c->multi_last = false;
+    c->multi_last = c->last_k16 = false;
     if (c->dirty) {
         HIP_TRY(hipMemsetAsync(c->islots, 0, SLOT_ALLOC_WORDS * sizeof(u64), c->stream));
         c->dirty = false;
@@ -819,24 +836,27 @@ std::array<const void *, 7 + MULTI_VARIANTS> pass_fns() {
             reinterpret_cast<const void *>(kth::k_main_multi<4, F32>),
             reinterpret_cast<const void *>(kth::k_main_multi<8, F32>)};
 }
+int pass_grid(const kth_ctx *c, const void *fn) {
+    int per = 4;
+    hipFuncAttributes fa;
+    if (hipFuncGetAttributes(&fa, fn) == hipSuccess && fa.numRegs > 0) {
+        const int alloc = (fa.numRegs + 7) / 8 * 8;
+        const int by_vgpr = std::min(8, 512 / alloc);
+        const int lds = (int)fa.sharedSizeBytes;
+        const int by_lds = lds > 0 ? (160 * 1024) / lds : 8;
+        per = std::max(1, std::min(by_vgpr, by_lds));
+    }
+    (void)hipGetLastError();
+    if (c->main_wg_per_cu > 0) per = c->main_wg_per_cu;
+    return c->num_cu * per;
+}
 void size_main_grids(kth_ctx *c) {
     // [key kind][TF] as c->main_grid, then the multi-rank variants as c->multi_grid
     const std::array<const void *, 7 + MULTI_VARIANTS> fns[2] = {pass_fns<false>(), pass_fns<true>()};
     for (int kind = 0; kind < 2; ++kind)
         for (int tf = 0; tf < 7 + MULTI_VARIANTS; ++tf) {
             if (!fns[kind][tf]) continue;
-            int per = 4;
-            hipFuncAttributes fa;
-            if (hipFuncGetAttributes(&fa, fns[kind][tf]) == hipSuccess && fa.numRegs > 0) {
-                const int alloc = (fa.numRegs + 7) / 8 * 8;
-                const int by_vgpr = std::min(8, 512 / alloc);
-                const int lds = (int)fa.sharedSizeBytes;
-                const int by_lds = lds > 0 ? (160 * 1024) / lds : 8;
-                per = std::max(1, std::min(by_vgpr, by_lds));
-            }
-            (void)hipGetLastError();
-            if (c->main_wg_per_cu > 0) per = c->main_wg_per_cu;
-            (tf < 7 ? c->main_grid[kind][tf] : c->multi_grid[kind][tf - 7]) = c->num_cu * per;
+            (tf < 7 ? c->main_grid[kind][tf] : c->multi_grid[kind][tf - 7]) = pass_grid(c, fns[kind][tf]);
         }
 }
 
@@ -989,6 +1009,7 @@ int kth_ctx_test_hook(kth_ctx *c, int hook, int64_t value) {
         if (value > (int64_t)1 << 40) return KTH_EINVAL;
         c->topk_seg_cap = (u64)value;
         return KTH_OK;
+    case KTH_HOOK_K16_MISS: c->k16_miss = value != 0; return KTH_OK;
     default: return KTH_EINVAL;
     }
 }
@@ -1002,7 +1023,7 @@ int kth_ctx_destroy(kth_ctx *c) {
     if (c->st) (void)hipFree(c->st);
     if (c->islots) (void)hipFree(c->islots);
     release_all(c->sample, c->cand, c->cand_rows, c->tk_segv, c->tk_segp, c->tk_wcnt, c->tk_wstart, c->staging,
-                c->topk, c->mstate, c->mslots, c->mcand);
+                c->topk, c->mstate, c->mslots, c->mcand, c->k16, c->k16st);
     if (c->d_mstatus) (void)hipFree(c->d_mstatus);
     if (c->h_mstatus) (void)hipHostFree(c->h_mstatus);
     if (c->d_status) (void)hipFree(c->d_status);
@@ -1146,13 +1167,8 @@ u64 multi_stride(u64 cap) { return (cap + 63) & ~(u64)63; }
 // buffers of the single select's capacity each (at 2^30 keys: 2^25 keys = 128
 // MiB a rank, 1 GiB for eight) beside the single select's own scratch, which
 // the per-level path uses.
-int reserve_multi(kth_ctx *c, int64_t n, int m) {
-    if (c->mslots.count == 0) {
-        KTH_TRY(c->mstate.reserve(2 * (u64)KTH_MULTI_MAX_RANKS));
-        KTH_TRY(c->mslots.reserve((u64)KTH_MULTI_MAX_RANKS * MSET_WORDS));
-        HIP_TRY(hipMemsetAsync(c->mstate.p, 0, c->mstate.count * sizeof(SelState), c->stream));
-        HIP_TRY(hipMemsetAsync(c->mslots.p, 0, c->mslots.count * sizeof(u64), c->stream));
-    }
+// [answer, error] per rank of a multi call, on the device and pinned
+int reserve_mstatus(kth_ctx *c) {
     if (!c->d_mstatus && hipMalloc(reinterpret_cast<void **>(&c->d_mstatus), 2 * KTH_MULTI_MAX_RANKS * sizeof(int32_t)) != hipSuccess) {
         (void)hipGetLastError();
         c->d_mstatus = nullptr;
@@ -1163,9 +1179,37 @@ int reserve_multi(kth_ctx *c, int64_t n, int m) {
         c->h_mstatus = nullptr;
         return KTH_ENOMEM;
     }
+    return KTH_OK;
+}
+
+int reserve_multi(kth_ctx *c, int64_t n, int m) {
+    if (c->mslots.count == 0) {
+        KTH_TRY(c->mstate.reserve(2 * (u64)KTH_MULTI_MAX_RANKS));
+        KTH_TRY(c->mslots.reserve((u64)KTH_MULTI_MAX_RANKS * MSET_WORDS));
+        HIP_TRY(hipMemsetAsync(c->mstate.p, 0, c->mstate.count * sizeof(SelState), c->stream));
+        HIP_TRY(hipMemsetAsync(c->mslots.p, 0, c->mslots.count * sizeof(u64), c->stream));
+    }
+    KTH_TRY(reserve_mstatus(c));
     if (n <= RADIX_MAX_N) return KTH_OK;
     KTH_TRY(reserve_window(c, n));
     return c->mcand.reserve((u64)m * multi_stride(cand_capacity(n)));
+}
+
+// The distinct ranks of a multi call (a duplicate is resolved once): dk[j],
+// first[j] = the first i with ks[i] == dk[j]; c->multi_set[i] = the j of ks[i].
+int distinct_ranks(kth_ctx *c, const int64_t *ks, int m, int64_t *dk, int *first) {
+    int D = 0;
+    for (int i = 0; i < m; ++i) {
+        int j = 0;
+        while (j < D && dk[j] != ks[i]) ++j;
+        if (j == D) {
+            dk[D] = ks[i];
+            first[D++] = i;
+        }
+        c->multi_set[i] = j;
+    }
+    c->multi_m = m;
+    return D;
 }
 
 template <bool F32>
@@ -1237,17 +1281,8 @@ int multi_async(kth_ctx *c, const int32_t *d_keys, int64_t n, const int64_t *ks,
     KTH_TRY(set_device(c));
     coop_tick(c);  // one selection, however many ranks
     int64_t dk[KTH_MULTI_MAX_RANKS];
-    int first[KTH_MULTI_MAX_RANKS], D = 0;
-    for (int i = 0; i < m; ++i) {  // duplicate ranks are resolved once
-        int j = 0;
-        while (j < D && dk[j] != ks[i]) ++j;
-        if (j == D) {
-            dk[D] = ks[i];
-            first[D++] = i;
-        }
-        c->multi_set[i] = j;
-    }
-    c->multi_m = m;
+    int first[KTH_MULTI_MAX_RANKS];
+    const int D = distinct_ranks(c, ks, m, dk, first);
     KTH_TRY(reserve_multi(c, n, D));
     int32_t *outs[KTH_MULTI_MAX_RANKS];
     for (int j = 0; j < D; ++j) outs[j] = d_out ? d_out + first[j] : nullptr;
@@ -1265,6 +1300,7 @@ int multi_async(kth_ctx *c, const int32_t *d_keys, int64_t n, const int64_t *ks,
             c->multi_dirty = false;
         }
         c->last_f32 = F32;
+        c->last_k16 = false;
         c->multi_cap = cand_capacity(n);
         ev_mark(c, c->ev_total, c->total_used);
         rc = run_multi_window<F32>(c, d_keys, n, dk, D, outs, d_status);
@@ -1353,6 +1389,151 @@ int multi_entry_async(kth_ctx *c, const int32_t *d_keys, int64_t n, const int64_
     return multi_async<F32>(c, d_keys, n, ks, m, d_out, false);
 }
 
+// ---------------------------------------------------------- 16-bit keys
+// kth_select_k16* / kth_select_multi_k16*: kth_k16.hpp's launches.  A single
+// select is a call with one rank.  Kernel boundaries only: no cooperative
+// launch, so the ctx's coop state is neither read nor counted down.
+bool k16_args_ok(const void *keys, int64_t n, const int64_t *ks, int m, int kind, const void *out) {
+    return kind >= KTH_K16_I16 && kind <= KTH_K16_BF16 && multi_args_ok(keys, n, ks, m, out);
+}
+
+template <int CV>
+const void *k16_main_fn() {
+    return reinterpret_cast<const void *>(kth::k16_main<CV>);
+}
+
+// Scratch of every k16 call, whatever n and m: the sample histogram, a set of
+// bins per rank and the states (~1.3 MB), the status words.
+int reserve_k16(kth_ctx *c) {
+    if (c->k16.count == 0) {
+        KTH_TRY(c->k16.reserve(K16_BUF_WORDS));
+        KTH_TRY(c->k16st.reserve(KTH_MULTI_MAX_RANKS));
+        HIP_TRY(hipMemsetAsync(c->k16.p, 0, c->k16.count * sizeof(u64), c->stream));
+        HIP_TRY(hipMemsetAsync(c->k16st.p, 0, c->k16st.count * sizeof(kth::K16State), c->stream));
+    }
+    KTH_TRY(reserve_mstatus(c));
+    if (!c->k16_ready) {
+        const void *hist[3] = {reinterpret_cast<const void *>(kth::k16_hist<0>), reinterpret_cast<const void *>(kth::k16_hist<1>),
+                               reinterpret_cast<const void *>(kth::k16_hist<2>)};
+        for (const void *f : hist) HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)K16_HIST_LDS));
+        const void *mains[3] = {k16_main_fn<0>(), k16_main_fn<1>(), k16_main_fn<2>()};
+        for (int v = 0; v < 3; ++v) c->k16_grid[v] = pass_grid(c, mains[v]);
+        c->k16_ready = true;
+    }
+    return KTH_OK;
+}
+
+template <int CV>
+int run_k16(kth_ctx *c, const uint16_t *keys, int64_t n, const int64_t *dk, int D, int kind, const kth::K16Out &out) {
+    const bool small = n <= kth::K16_SMALL_N;
+    const int64_t s = small ? n : sample_size(n);
+    const u64 nchunks = ((u64)s + kth::K16_CHUNK - 1) / kth::K16_CHUNK;
+    const u64 stride = small ? (u64)kth::K16_CHUNK : (u64)n / nchunks;
+    const uint32_t nl = kth::k16_nl(kind), top = kth::k16_top(kind);
+    const uint32_t nl2 = nl | nl << 16, top2 = top | top << 16;
+    uint32_t *shist = reinterpret_cast<uint32_t *>(c->k16.p);
+    u64 *bins = c->k16.p + K16_SHIST_WORDS;
+    const int hist_grid = (int)(((u64)s + kth::K16_HIST_PER_WG - 1) / kth::K16_HIST_PER_WG);
+
+    if (small) ev_main(c);
+    kth::k16_hist<CV><<<hist_grid, kth::K16_HIST_BLK, K16_HIST_LDS, c->stream>>>(keys, (u64)n, (u64)s, stride, nl2, top2, shist);
+    if (small) ev_main(c);
+    kth::K16PickArgs pa;
+    memset(&pa, 0, sizeof pa);
+    pa.shist = shist;
+    pa.st = c->k16st.p;
+    pa.D = D;
+    pa.small = small;
+    pa.miss = c->k16_miss;
+    pa.n = (u64)n;
+    pa.C = (uint32_t)(kth::K16_FIELDS / 2) / (D <= 1 ? 1u : D <= 2 ? 2u : D <= 4 ? 4u : 8u);
+    pa.top = top;
+    for (int j = 0; j < D; ++j) {
+        pa.k[j] = (u64)dk[j];
+        if (!small) window_ranks(n, dk[j], s, &pa.rlo[j], &pa.rhi[j]);
+    }
+    pa.out = out;
+    kth::k16_pick<<<1, kth::K16_HIST_BLK, 0, c->stream>>>(pa);
+    if (!small) {
+        const kth::K16Args ma{keys, (u64)n, D, nl2, top2, c->k16st.p, bins};
+        const kth::K16FinArgs fa{c->k16st.p, bins, top, out};
+        for (int pass = 0; pass < kth::K16_PASSES; ++pass) {  // (the later ones return at once when every rank is settled)
+            if (pass == 0) ev_main(c);
+            kth::k16_main<CV><<<c->k16_grid[CV], kth::BLK, 0, c->stream>>>(ma);
+            if (pass == 0) ev_main(c);
+            kth::k16_finish<<<D, kth::K16_HIST_BLK, 0, c->stream>>>(fa);
+        }
+    }
+    return launch_check();
+}
+
+// d_out: m answers on the device, or null; status: also [bits, error] per
+// distinct rank into c->d_mstatus.
+int k16_async(kth_ctx *c, const uint16_t *d_keys, int64_t n, const int64_t *ks, int m, int kind, uint16_t *d_out,
+              bool status) {
+    KTH_TRY(set_device(c));
+    int64_t dk[KTH_MULTI_MAX_RANKS];
+    int first[KTH_MULTI_MAX_RANKS];
+    const int D = distinct_ranks(c, ks, m, dk, first);
+    KTH_TRY(reserve_k16(c));
+    if (c->k16_dirty) {
+        HIP_TRY(hipMemsetAsync(c->k16.p, 0, c->k16.count * sizeof(u64), c->stream));
+        c->k16_dirty = false;
+    }
+    c->last_k16 = true;
+    c->multi_last = false;
+    c->k16_kind = kind;
+    kth::K16Out out;
+    memset(&out, 0, sizeof out);
+    out.m = m;
+    out.kind = kind;
+    for (int i = 0; i < m; ++i) out.set[i] = c->multi_set[i];
+    out.d_out = d_out;
+    out.d_status = status ? c->d_mstatus : nullptr;
+    ev_mark(c, c->ev_total, c->total_used);
+    const int rc = kind == KTH_K16_U16   ? run_k16<0>(c, d_keys, n, dk, D, kind, out)
+                   : kind == KTH_K16_I16 ? run_k16<1>(c, d_keys, n, dk, D, kind, out)
+                                         : run_k16<2>(c, d_keys, n, dk, D, kind, out);
+    ev_mark(c, c->ev_total, c->total_used);
+    if (rc != KTH_OK) c->k16_dirty = true;
+    return rc;
+}
+
+// The synchronous call through a ctx: host keys are staged, the status words
+// are read once.
+int k16_ctx(kth_ctx *c, const void *keys, int64_t n, const int64_t *ks, int m, int kind, uint16_t *out) {
+    if (!c || !k16_args_ok(keys, n, ks, m, kind, out)) return KTH_EINVAL;
+    KTH_TRY(set_device(c));
+    const uint16_t *dk = static_cast<const uint16_t *>(keys);
+    if (!is_device_ptr(keys)) {
+        KTH_TRY(c->staging.reserve(((u64)n + 1) / 2));
+        HIP_TRY(hipMemcpyAsync(c->staging.p, keys, (size_t)n * 2, hipMemcpyHostToDevice, c->stream));
+        dk = reinterpret_cast<const uint16_t *>(c->staging.p);
+    }
+    KTH_TRY(k16_async(c, dk, n, ks, m, kind, nullptr, true));
+    HIP_TRY(hipMemcpyAsync(c->h_mstatus, c->d_mstatus, 2 * KTH_MULTI_MAX_RANKS * sizeof(int32_t), hipMemcpyDeviceToHost,
+                           c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < m; ++i)
+        if (c->h_mstatus[2 * c->multi_set[i] + 1] != 0) {
+            c->k16_dirty = true;
+            return KTH_EINTERNAL;
+        }
+    for (int i = 0; i < m; ++i) out[i] = (uint16_t)c->h_mstatus[2 * c->multi_set[i]];
+    return KTH_OK;
+}
+
+int k16_oneshot(const void *keys, int64_t n, const int64_t *ks, int m, int kind, uint16_t *out) {
+    if (!k16_args_ok(keys, n, ks, m, kind, out)) return KTH_EINVAL;
+    KTH_TRY(thread_ctx());
+    return k16_ctx(tl_ctx, keys, n, ks, m, kind, out);
+}
+
+int k16_entry_async(kth_ctx *c, const void *d_keys, int64_t n, const int64_t *ks, int m, int kind, uint16_t *d_out) {
+    if (!c || !k16_args_ok(d_keys, n, ks, m, kind, d_out)) return KTH_EINVAL;
+    return k16_async(c, static_cast<const uint16_t *>(d_keys), n, ks, m, kind, d_out, false);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1399,6 +1580,34 @@ int kth_ctx_reserve_multi(kth_ctx *c, int64_t n, int m) {
     return reserve_multi(c, n, m);
 }
 
+int kth_select_k16(const void *keys, int64_t n, int64_t k, int kind, uint16_t *out) {
+    return k16_oneshot(keys, n, &k, 1, kind, out);
+}
+int kth_select_k16_ctx(kth_ctx *c, const void *keys, int64_t n, int64_t k, int kind, uint16_t *out) {
+    return k16_ctx(c, keys, n, &k, 1, kind, out);
+}
+int kth_select_k16_async(kth_ctx *c, const void *d_keys, int64_t n, int64_t k, int kind, uint16_t *d_out) {
+    return k16_entry_async(c, d_keys, n, &k, 1, kind, d_out);
+}
+int kth_select_multi_k16(const void *keys, int64_t n, const int64_t *ks, int m, int kind, uint16_t *out) {
+    return k16_oneshot(keys, n, ks, m, kind, out);
+}
+int kth_select_multi_k16_ctx(kth_ctx *c, const void *keys, int64_t n, const int64_t *ks, int m, int kind,
+                             uint16_t *out) {
+    return k16_ctx(c, keys, n, ks, m, kind, out);
+}
+int kth_select_multi_k16_async(kth_ctx *c, const void *d_keys, int64_t n, const int64_t *ks, int m, int kind,
+                               uint16_t *d_out) {
+    return k16_entry_async(c, d_keys, n, ks, m, kind, d_out);
+}
+int kth_ctx_reserve_k16(kth_ctx *c, int64_t n, int m) {
+    if (!c || n < 0 || m < 1 || m > KTH_MULTI_MAX_RANKS) return KTH_EINVAL;
+    KTH_TRY(set_device(c));
+    return reserve_k16(c);
+}
+uint16_t kth_k16_order_key(uint16_t bits, int kind) { return kth::k16_key_of_bits(bits, kind); }
+uint16_t kth_k16_of_order_key(uint16_t key, int kind) { return kth::k16_bits_of_key(key, kind); }
+
 uint32_t kth_f32_order_key(float x) {
     uint32_t b;
     memcpy(&b, &x, sizeof b);
@@ -1444,9 +1653,31 @@ int fetch_stats(kth_ctx *c, const SelState *d_state, u64 capacity, kth_stats *ou
     return KTH_OK;
 }
 
+// Rank set j of the last 16-bit call: the window as order keys, the answer's bits.
+int fetch_stats_k16(kth_ctx *c, int j, kth_stats *out) {
+    KTH_TRY(set_device(c));
+    kth::K16State *h = reinterpret_cast<kth::K16State *>(c->h_state);
+    static_assert(sizeof(kth::K16State) <= sizeof(SelState), "the pinned state buffer holds either");
+    HIP_TRY(hipMemcpyAsync(h, c->k16st.p + j, sizeof *h, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    memset(out, 0, sizeof *out);
+    out->path = (int32_t)h->path;
+    out->mode = (int32_t)h->mode;
+    out->lo_key = kth::k16_key_of_ord(h->lo, c->k16_kind);
+    out->hi_key = kth::k16_key_of_ord(h->hi, c->k16_kind);
+    out->n = h->n;
+    out->k = h->k;
+    out->cnt_lt = h->cnt_lt;
+    out->candidates = h->inside;
+    out->answer = (int32_t)kth::k16_bits_of_ord(h->answer, c->k16_kind);
+    out->error = (int32_t)h->error;
+    return KTH_OK;
+}
+
 // rank i of the last multi call: its final state is state 0 of its set
 int multi_stats(kth_ctx *c, int i, kth_stats *out) {
     if (!c || !out || i < 0 || i >= c->multi_m) return KTH_EINVAL;
+    if (c->last_k16) return fetch_stats_k16(c, c->multi_set[i], out);
     return fetch_stats(c, c->mstate.p + 2 * (size_t)c->multi_set[i], c->multi_cap, out);
 }
 
@@ -1458,7 +1689,7 @@ int kth_ctx_multi_stats(kth_ctx *c, int i, kth_stats *out) { return multi_stats(
 
 int kth_ctx_last_stats(kth_ctx *c, kth_stats *out) {
     if (!c || !out) return KTH_EINVAL;
-    if (c->multi_last) return multi_stats(c, c->multi_m - 1, out);
+    if (c->multi_last || c->last_k16) return multi_stats(c, c->multi_m - 1, out);
     if (c->last_state < 0) return KTH_EINVAL;
     return fetch_stats(c, c->st + c->last_state, c->cand.count, out);
 }
@@ -1906,7 +2137,7 @@ static int launch_dresult(kth_ctx *c, int L, int32_t *d_out, uint32_t early) {
                                                             ISLOT_WORDS + HSLOT_WORDS, early);
     c->last_state = L % 2;
     c->last_f32 = false;  // (the sharded protocol is int32 only)
-    c->multi_last = false;
+    c->multi_last = c->last_k16 = false;
     return launch_check();
 }
 

@@ -37,9 +37,16 @@ from ._lib import (  # noqa: F401
     KTH_ENODEV,
     KTH_HOOK_FAULT_BARRIER,
     KTH_HOOK_FAULT_TOPK_RANK,
+    KTH_HOOK_K16_MISS,
     KTH_HOOK_TOPK_SEG_CAP,
     KTH_MULTI_MAX_RANKS,
+    KTH_K16_BF16,
+    KTH_K16_F16,
+    KTH_K16_I16,
+    KTH_K16_U16,
     KTH_OK,
+    KTH_PATH_K16,
+    KTH_PATH_K16_FALLBACK,
     KTH_PATH_LDS,
     KTH_PATH_RADIX,
     KTH_PATH_WINDOW,
@@ -123,6 +130,45 @@ def _multi_host_keys(keys, f32):
     if f32:
         _need_f32(keys, "keys")
     return keys
+
+
+K16_KINDS = {"i16": KTH_K16_I16, "u16": KTH_K16_U16, "f16": KTH_K16_F16, "bf16": KTH_K16_BF16}
+_K16_OF_DTYPE = {"int16": KTH_K16_I16, "uint16": KTH_K16_U16, "float16": KTH_K16_F16, "bfloat16": KTH_K16_BF16}
+_K16_NUMPY = {KTH_K16_I16: np.int16, KTH_K16_U16: np.uint16, KTH_K16_F16: np.float16}
+
+
+def _k16_kind(x, kind, what="keys"):
+    """The KTH_K16_* kind of 16-bit keys: from the dtype (torch int16 / uint16 /
+    float16 / bfloat16, numpy int16 / uint16 / float16), or `kind` ("i16", "u16",
+    "f16", "bf16" or a KTH_K16_* value) over any 2-byte dtype -- a numpy uint16
+    array with kind="bf16" carries bfloat16 bits.  Anything else is a TypeError:
+    nothing is converted."""
+    dt = getattr(x, "dtype", None)
+    name = str(dt).rsplit(".", 1)[-1] if dt is not None else None
+    if name is not None and name not in _K16_OF_DTYPE:
+        raise TypeError(f"{what} must be int16, uint16, float16 or bfloat16, got {dt}")
+    if kind is None:
+        if name is None:
+            raise TypeError(f"{what} carries no dtype: pass kind=")
+        return _K16_OF_DTYPE[name]
+    if isinstance(kind, str):
+        if kind not in K16_KINDS:
+            raise ValueError(f"unknown 16-bit key kind {kind!r}")
+        return K16_KINDS[kind]
+    return int(kind)
+
+
+def _k16_host_keys(keys):
+    return np.ascontiguousarray(keys) if isinstance(keys, np.ndarray) else keys
+
+
+def _k16_values(bits, kind):
+    """The answers' bits (numpy uint16 array) as exact values: int16 / uint16 /
+    float16, and for bfloat16 np.float32 whose upper 16 bits are the answer."""
+    bits = np.ascontiguousarray(bits, dtype=np.uint16)
+    if kind == KTH_K16_BF16:
+        return (bits.astype(np.uint32) << np.uint32(16)).view(np.float32)
+    return bits.view(_K16_NUMPY[kind])
 
 
 def _stream_handle(stream):
@@ -250,6 +296,45 @@ class Selector:
         check(LIB.kth_ctx_multi_stats(self._ctx, int(i), ctypes.byref(st)), "kth_ctx_multi_stats")
         return st.as_dict()
 
+    # -- 16-bit keys ---------------------------------------------------------
+    def select16(self, keys, k, n=None, kind=None):
+        """k-th smallest (1-based) of int16 / uint16 / float16 / bfloat16 keys (host
+        numpy array or device tensor; `kind` as _k16_kind): a numpy scalar of the
+        keys' type with the answer's exact bits (bfloat16: np.float32)."""
+        return self.select16_multi(keys, [k], n=n, kind=kind)[0]
+
+    def select16_async(self, d_keys, n, k, d_out, kind=None):
+        """Enqueue a 16-bit select of device keys; the answer's bits land in the
+        2-byte element *d_out."""
+        self.select16_multi_async(d_keys, n, [k], d_out, kind=kind)
+
+    def select16_multi(self, keys, ks, n=None, kind=None):
+        """The ks[i]-th smallest of 16-bit keys for every rank in ks, one streaming
+        pass per group of KTH_MULTI_MAX_RANKS ranks (kth_select_multi_k16_ctx)."""
+        kind = _k16_kind(keys, kind)
+        keys = _k16_host_keys(keys)
+        if n is None:
+            n = _numel(keys)
+        groups = list(_rank_groups(ks))
+        out = np.empty(sum(len(g) for _, g in groups), dtype=np.uint16)
+        for at, g in groups:
+            check(LIB.kth_select_multi_k16_ctx(self._ctx, _ptr(keys), int(n), g, len(g), kind, out[at:].ctypes.data),
+                  "kth_select_multi_k16_ctx")
+        return _k16_values(out, kind)
+
+    def select16_multi_async(self, d_keys, n, ks, d_out, kind=None):
+        """Enqueue the 16-bit selection of every rank in ks over device keys; answer
+        i's bits land in the 2-byte element d_out[i] (len(ks) contiguous elements)."""
+        kind = _k16_kind(d_keys, kind, "d_keys")
+        _k16_kind(d_out, kind, "d_out")
+        for at, g in _rank_groups(ks):
+            check(LIB.kth_select_multi_k16_async(self._ctx, _ptr(d_keys), int(n), g, len(g), kind, _ptr(d_out) + 2 * at),
+                  "kth_select_multi_k16_async")
+
+    def reserve16(self, n, m=1):
+        """Pre-size the scratch of 16-bit calls (kth_ctx_reserve_k16)."""
+        check(LIB.kth_ctx_reserve_k16(self._ctx, int(n), min(int(m), KTH_MULTI_MAX_RANKS)), "kth_ctx_reserve_k16")
+
     def coop(self):
         """True while the ctx runs the cooperative grid-barrier kernels (kth_ctx_coop)."""
         r = LIB.kth_ctx_coop(self._ctx)
@@ -346,6 +431,27 @@ def kth_select_multi(keys, ks, f32=False):
     for at, g in groups:
         check(fn(_ptr(keys), int(_numel(keys)), g, len(g), out[at:].ctypes.data), what)
     return out
+
+
+def kth_select16_multi(keys, ks, kind=None):
+    """One-shot kth_select_multi_k16 over 16-bit keys, as Selector.select16_multi."""
+    kind = _k16_kind(keys, kind)
+    keys = _k16_host_keys(keys)
+    groups = list(_rank_groups(ks))
+    out = np.empty(sum(len(g) for _, g in groups), dtype=np.uint16)
+    for at, g in groups:
+        check(LIB.kth_select_multi_k16(_ptr(keys), int(_numel(keys)), g, len(g), kind, out[at:].ctypes.data),
+              "kth_select_multi_k16")
+    return _k16_values(out, kind)
+
+
+def kth_select16(keys, k, kind=None):
+    """One-shot kth_select_k16: the k-th smallest of 16-bit keys, as Selector.select16."""
+    kind = _k16_kind(keys, kind)
+    keys = _k16_host_keys(keys)
+    out = np.empty(1, dtype=np.uint16)
+    check(LIB.kth_select_k16(_ptr(keys), int(_numel(keys)), int(k), kind, out.ctypes.data), "kth_select_k16")
+    return _k16_values(out, kind)[0]
 
 
 class ShardedSelector:

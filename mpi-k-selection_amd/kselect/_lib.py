@@ -20,6 +20,8 @@ KTH_EINTERNAL = -5
 KTH_ECOMM = -6
 
 KTH_PATH_LDS, KTH_PATH_RADIX, KTH_PATH_WINDOW, KTH_PATH_WINDOW_FALLBACK = 1, 2, 3, 4
+KTH_PATH_K16, KTH_PATH_K16_FALLBACK = 5, 6
+KTH_K16_I16, KTH_K16_U16, KTH_K16_F16, KTH_K16_BF16 = 0, 1, 2, 3
 KTH_STATS_WORDS = 8 + 2 * 2048
 KTH_DIST_DONE = 3  # kth_dist_level: no collective left, call kth_dist_result
 KTH_DIST_MAX_LEVELS = 3
@@ -28,6 +30,7 @@ KTH_TOPK_MAX_COLS = 4096
 KTH_MULTI_MAX_RANKS = 8
 # kth_ctx_test_hook (tests only): fault injectors, off in every new ctx
 KTH_HOOK_FAULT_TOPK_RANK, KTH_HOOK_FAULT_BARRIER, KTH_HOOK_TOPK_SEG_CAP = 1, 2, 3
+KTH_HOOK_K16_MISS = 4
 
 c_i32p = ctypes.POINTER(ctypes.c_int32)
 c_u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -100,6 +103,15 @@ PROTOS = {
     "kth_select_multi_f32_async": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_i64p, ctypes.c_int, c_vp]),
     "kth_ctx_reserve_multi": (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int]),
     "kth_ctx_multi_stats": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.POINTER(KthStats)]),
+    "kth_k16_order_key": (ctypes.c_uint16, [ctypes.c_uint16, ctypes.c_int]),
+    "kth_k16_of_order_key": (ctypes.c_uint16, [ctypes.c_uint16, ctypes.c_int]),
+    "kth_select_k16": (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, c_vp]),
+    "kth_select_k16_ctx": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, c_vp]),
+    "kth_select_k16_async": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, c_vp]),
+    "kth_select_multi_k16": (ctypes.c_int, [c_vp, ctypes.c_int64, c_i64p, ctypes.c_int, ctypes.c_int, c_vp]),
+    "kth_select_multi_k16_ctx": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_i64p, ctypes.c_int, ctypes.c_int, c_vp]),
+    "kth_select_multi_k16_async": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_i64p, ctypes.c_int, ctypes.c_int, c_vp]),
+    "kth_ctx_reserve_k16": (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int]),
     "kth_f32_order_key": (ctypes.c_uint32, [ctypes.c_float]),
     "kth_f32_of_order_key": (ctypes.c_float, [ctypes.c_uint32]),
     "kth_ctx_last_stats": (ctypes.c_int, [c_vp, ctypes.POINTER(KthStats)]),
