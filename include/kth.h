@@ -99,18 +99,49 @@ int kth_select_i32_ctx(kth_ctx *ctx, const int32_t *keys, int64_t n, int64_t k, 
 /* Asynchronous select: d_keys and d_out are device memory; the work is
  * enqueued on the ctx stream and *d_out is written on the device.  No host
  * synchronisation and no allocation once the ctx is reserved for n
- * (graph-capturable). */
+ * (graph-capturable).
+ *
+ * Graph capture (this call, kth_select_f32_async, kth_select_multi_*_async and
+ * kth_select_{,multi_}k16_async; tests/test_gpu_graph.py pins every line):
+ *   - Capture on the stream the ctx is bound to, after the ctx has been
+ *     reserved for that form and size (kth_ctx_reserve, kth_ctx_reserve_multi,
+ *     kth_ctx_reserve_k16): the call then allocates and synchronises nothing.
+ *   - While a graph that used the ctx is alive, make no call that grows one of
+ *     the ctx's buffers (a larger n or m than reserved for, a first top-k):
+ *     growing frees the old buffer, whose address the graph holds.  Destroy
+ *     the graph before the ctx.
+ *   - A graph holds the launches as they were enqueued: the ctx's cooperative
+ *     or per-level mode, its test hooks and its timing switch (keep timing
+ *     off while capturing) are frozen in it as they were at capture; changing
+ *     them later changes no replay.
+ *   - Any number of calls per graph, of any of these forms.  Every launch
+ *     sequence leaves the ctx's scratch as it found it, so a replay may follow
+ *     itself, another graph of the same ctx, or any eager call on the same ctx
+ *     and stream (selects, multi and 16-bit calls, top-k, rows), in any order
+ *     and number.  The same holds after a call whose error was only reported
+ *     (the test hook KTH_HOOK_FAULT_BARRIER: its barriers complete).  A grid
+ *     barrier that really timed out is excluded: workgroups may then still
+ *     add into slots that others clear, so the scratch is not known clean
+ *     and the asynchronous forms do not re-zero it: after a stats().error of
+ *     64 from an asynchronous call, go on with a fresh ctx.
+ *   - kth_ctx_last_stats reports the launches that ran last on the stream,
+ *     replayed or eager (the device records it).  kth_ctx_multi_stats(ctx, i)
+ *     maps i to a rank by the last multi or 16-bit call made -- or captured --
+ *     through the API, and is KTH_EINVAL when what ran last is not a call of
+ *     that form and key kind.
+ * Top-k, the rows kernels and the sharded protocol are not claimed capturable. */
 int kth_select_i32_async(kth_ctx *ctx, const int32_t *d_keys, int64_t n, int64_t k, int32_t *d_out);
 
 /* --- float32 keys (one array) ------------------------------------------------
  * The _f32 twins of the three selects above: same error codes (KTH_EINVAL
  * before any device work, KTH_ENODEV without a GPU), same stream behaviour,
  * same cooperative back-off rule, the async form graph-capturable once the ctx
- * is reserved.  Order, the one kth_select_rows_f32 uses: IEEE total order on
- * the bit patterns, -0.0 < +0.0, subnormals distinct, every NaN (either sign,
- * any payload) above +inf and equal to every other NaN.  The returned value
- * has the bit pattern of an input element, except that a NaN comes back as the
- * canonical quiet NaN 0x7FC00000.  The input is not modified.
+ * is reserved (under the conditions at kth_select_i32_async).  Order, the one
+ * kth_select_rows_f32 uses: IEEE total order on the bit patterns, -0.0 <
+ * +0.0, subnormals distinct, every NaN (either sign, any payload) above +inf
+ * and equal to every other NaN.  The returned value has the bit pattern of an
+ * input element, except that a NaN comes back as the canonical quiet NaN
+ * 0x7FC00000.  The input is not modified.
  * The kernels are the int32 kernels instantiated for float32 words: a word
  * becomes an ordered int32 right after its load (integer operations only) and
  * a value turns back into a float only where it leaves the library. */
@@ -138,8 +169,9 @@ float kth_f32_of_order_key(uint32_t key);
  * host or device keys and are synchronous; the _async form takes device
  * memory only, enqueues on the ctx stream, makes no host synchronisation, and
  * no allocation once kth_ctx_reserve_multi(ctx, n, m) or an earlier call of
- * the same size has sized the scratch (graph-capturable, as
- * kth_select_i32_async).
+ * the same size has sized the scratch (graph-capturable, under the conditions
+ * at kth_select_i32_async; any number of distinct ranks, and a duplicate's
+ * copy is a node of the graph).
  * One pass: for n > 4 Mi keys on a ctx that runs the cooperative kernels, the
  * call reads the input from HBM ONCE: a sample phase per distinct rank, one
  * streaming launch that serves every rank's window from each loaded tile, a
@@ -199,7 +231,8 @@ int kth_ctx_multi_stats(kth_ctx *ctx, int i, kth_stats *st);
  * KTH_EINTERNAL); the _async forms take device memory only, enqueue on the ctx
  * stream, never synchronise, and allocate nothing once
  * kth_ctx_reserve_k16(ctx, n, m) or any earlier k16 call has run (the scratch,
- * ~1.3 MB, does not depend on n or m), so they are graph-capturable.  The
+ * ~1.3 MB, does not depend on n or m), so they are graph-capturable (under the
+ * conditions at kth_select_i32_async; KTH_HOOK_K16_MISS is frozen too).  The
  * answer has the bit pattern of an input element, a NaN comes back canonical.
  * d_keys needs only 2-byte alignment.  Counts and ranks are 64-bit.
  * n <= 32768: the full 65536-bin histogram decides.  Above: a sample window

@@ -52,16 +52,15 @@ int gather_grid(u64 nchunks) {
 }
 constexpr size_t ISLOT_WORDS = 3 * (size_t)kth::STATS_WORDS + 2;  // 3 slots + cand_count + pad
 // after the islots, in the same allocation: k_head's and k_finish's level
-// slots (zero between selects), then the grid-barrier words (never cleared by
-// a select: the barrier resets itself)
+// slots and PreHist (zero between selects: k_finish leaves them so), then the
+// grid-barrier words (never cleared by a select: the barrier resets itself)
 constexpr size_t HSLOT_OFF = ISLOT_WORDS;
 constexpr size_t HSLOT_WORDS = (size_t)kth::HEAD_LEVELS * kth::STATS_WORDS;
-constexpr size_t FSLOT_OFF = HSLOT_OFF + HSLOT_WORDS;  // two sets, alternate k_finish launches
+constexpr size_t FSLOT_OFF = HSLOT_OFF + HSLOT_WORDS;
 constexpr size_t FSLOT_WORDS = (size_t)kth::FIN_LEVELS * kth::STATS_WORDS;
-constexpr size_t PRE_OFF = FSLOT_OFF + 2 * FSLOT_WORDS;  // two PreHist sets (u32 words), alternate selects
-constexpr size_t PRE_SET_WORDS = (size_t)kth::PRE_WORDS / 2;  // (in u64 words)
-static_assert(kth::PRE_WORDS % 4 == 0, "PreHist sets stay 16-byte aligned");
-constexpr size_t ZERO_WORDS = PRE_OFF + 2 * PRE_SET_WORDS;
+constexpr size_t PRE_OFF = FSLOT_OFF + FSLOT_WORDS;  // PreHist (u32 words)
+static_assert(kth::PRE_WORDS % 4 == 0 && PRE_OFF % 2 == 0, "k_finish clears PreHist in 16-byte words");
+constexpr size_t ZERO_WORDS = PRE_OFF + (size_t)kth::PRE_WORDS / 2;  // (in u64 words)
 constexpr size_t BAR_OFF = ZERO_WORDS;
 constexpr size_t TAIL_OFF = BAR_OFF + kth::BAR_WORDS / 2;  // k_finish's tail keys (FIN_LDS_KEYS u32)
 constexpr size_t SLOT_ALLOC_WORDS = TAIL_OFF + kth::FIN_LDS_KEYS / 2;
@@ -157,7 +156,6 @@ struct kth_ctx {
     int fin_grid = 256;        // k_finish workgroups (one per CU; KTH_FIN_GRID)
     uint32_t head_slack64 = (uint32_t)(HEAD_SLACK * 64);
     uint32_t head_abs_div = 1024;  // plain select: early-window floor s / head_abs_div sample keys (KTH_HEAD_ABS; 0 = off)
-    int fin_set = 0;           // k_finish slot set of the next launch (the other one is cleared by it)
     bool pre_hist = true;      // k_main<0> histograms the candidates' first digit for k_finish (KTH_PRE_HIST=0: off)
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -175,21 +173,21 @@ struct kth_ctx {
     kth::TkSeg tk_seg{};  // the segments of the next launch_main<5/6>
     DevBuf<int32_t> staging;
     DevBuf<u64> topk;  // top-k chunk counts, bases, [need, error]
-    int32_t *d_status = nullptr;  // [answer, error]
+    int32_t *d_status = nullptr;  // [answer, error, the last-call word (LastCall), -]
     int32_t *h_status = nullptr;  // pinned
     SelState *h_state = nullptr;  // pinned
-    int last_state = -1;
+    int last_state = -1;          // the state the last single select enqueued here ends in (top-k reads it)
+    uint32_t multi_tag = 0;       // while a multi call sends its ranks through the single select's launches: its LastCall word
     // multi-rank calls: a set per rank (states, slots, candidates), [answer, error] per rank
     DevBuf<SelState> mstate;  // 2 per rank
     DevBuf<u64> mslots;       // MSET_WORDS per rank, zero between calls
     DevBuf<uint32_t> mcand;   // per rank: the candidates, mcand_stride words apart
     int32_t *d_mstatus = nullptr, *h_mstatus = nullptr;  // 2 words per rank (device / pinned)
     int multi_m = 0;          // ranks of the last multi call (0: none yet)
+    uint32_t multi_word = 0;  // ... and its LastCall word (form, key kind): the rank map below belongs to that call
     int multi_set[KTH_MULTI_MAX_RANKS] = {};  // ... and the set that resolved each (duplicates share one)
     u64 multi_cap = 0;        // ... and its per-rank candidate capacity
-    bool multi_last = false;  // the last selection on this ctx was a multi call (kth_ctx_last_stats: its last rank)
     bool multi_dirty = false; // a multi call was cut short or failed: re-zero mslots
-    bool last_f32 = false;    // the last select's keys were float32 (kth_stats.answer: its bits)
     // 16-bit keys: the sample histogram and the ranks' sets, their states; the
     // call's rank -> set map and status words are the multi call's
     DevBuf<u64> k16;
@@ -198,13 +196,12 @@ struct kth_ctx {
     bool k16_ready = false;   // grids sized, k16_hist's LDS granted
     bool k16_dirty = false;   // a k16 call was cut short or failed: re-zero its scratch
     bool k16_miss = false;    // KTH_HOOK_K16_MISS (tests): the sample phase publishes an empty window
-    bool last_k16 = false;    // the last selection on this ctx had 16-bit keys
-    int k16_kind = 0;         // ... of this kind
     // timing: event pairs around the streaming pass and around whole selects
     bool timing = false;
     std::vector<hipEvent_t> ev_main, ev_total;
     int main_used = 0, total_used = 0;
     bool dirty = false;  // a launch sequence was cut short: re-zero the slots
+    bool count_kept = false;  // a per-level top-k select left the candidate count: kth_topk_* clears it after k_topk_cands
     bool dist_zero = false;  // sharded: the bound slots still need clearing
     bool dist_open = false;  // sharded: begun, kth_dist_result not yet enqueued
     bool dist_coop_window = false;  // sharded: the window came from k_head (state carried, no pick left)
@@ -230,6 +227,29 @@ namespace {
 
 // (islot(i) in the comments below: slot i of the three in c->islots)
 u64 *cand_count(kth_ctx *c) { return c->islots + 3 * (size_t)kth::STATS_WORDS; }
+
+// LastCall: which selection ran last on the ctx, for kth_ctx_last_stats and
+// kth_ctx_multi_stats -- a word on the device, written by the last launch of
+// every selection, because the host's own record only knows the calls it
+// enqueued: a replayed graph runs a call again without the host.  The form, the
+// key kind and where the final state lies: a single select's state (0 / 1), the
+// set of a multi or 16-bit call's last rank.
+enum : uint32_t { LAST_NONE = 0, LAST_SINGLE = 1, LAST_MULTI = 2, LAST_K16 = 3 };
+struct LastCall {
+    uint32_t form;
+    bool f32;
+    int index, k16_kind;
+};
+uint32_t last_word(uint32_t form, bool f32, int index, int k16_kind = 0) {
+    return form | (f32 ? 4u : 0u) | (uint32_t)index << 4 | (uint32_t)k16_kind << 8;
+}
+LastCall last_of_word(uint32_t w) { return LastCall{w & 3u, (w & 4u) != 0, (int)(w >> 4 & 15u), (int)(w >> 8 & 3u)}; }
+uint32_t *d_last(kth_ctx *c) { return reinterpret_cast<uint32_t *>(c->d_status + 2); }
+// a single select that ends in state `state` (as a rank of a multi call: that call's word)
+template <bool F32>
+uint32_t single_word(const kth_ctx *c, int state) {
+    return c->multi_tag ? c->multi_tag : last_word(LAST_SINGLE, F32, state);
+}
 
 int set_device(kth_ctx *c) {
     HIP_TRY(hipSetDevice(c->device));
@@ -474,7 +494,7 @@ int run_small(kth_ctx *c, const int32_t *keys, int64_t n, int64_t k, int32_t *d_
     c->last_state = 1;
     ev_main(c);
     kth::k_small<F32><<<1, kth::SMALL_BLOCK, (size_t)n * 4, c->stream>>>(keys, (u64)n, (u64)k, d_out, d_status,
-                                                                    c->st + 1);
+                                                                    c->st + 1, d_last(c), single_word<F32>(c, 1));
     ev_main(c);
     return launch_check();
 }
@@ -495,29 +515,24 @@ kth::CoopArgs coop_args(kth_ctx *c, u64 slot_off, int32_t *d_out, int32_t *d_sta
     return x;
 }
 
-// k_finish: the finish phase in one launch, on slot set fin_set; it clears the
-// other set and the sample phase's slots for the next select
+// k_finish: the finish phase in one launch.  It leaves its slots, PreHist and
+// the sample phase's slots zero, so nothing here depends on what ran before:
+// the launch can run again as enqueued.
 constexpr size_t FIN_DYN_LDS = (size_t)kth::FIN_LDS_KEYS * 4;
-uint32_t *pre_set(kth_ctx *c, int set) {
-    return reinterpret_cast<uint32_t *>(c->islots + PRE_OFF + (size_t)set * PRE_SET_WORDS);
-}
+uint32_t *pre_words(kth_ctx *c) { return reinterpret_cast<uint32_t *>(c->islots + PRE_OFF); }
 
-// with_pre: this select's k_main<0> histogrammed the candidates' first digit
-// into PreHist set fin_set
+// last: the LastCall word the launch leaves
+// with_pre: this select's k_main<0> histogrammed the candidates' first digit into PreHist
 // head_slots: the sample phase's slots this launch clears (null: the ctx's own)
 template <bool F32>
-void launch_finish(kth_ctx *c, StepArgs a, int32_t *d_out, int32_t *d_status, bool with_pre = false,
+void launch_finish(kth_ctx *c, const StepArgs &a, int32_t *d_out, int32_t *d_status, uint32_t last, bool with_pre = false,
                    u64 *head_slots = nullptr) {
-    const size_t mine = FSLOT_OFF + (size_t)c->fin_set * FSLOT_WORDS;
-    a.stats_zero = c->islots + FSLOT_OFF + (size_t)(1 - c->fin_set) * FSLOT_WORDS;
-    a.zero_words = FSLOT_WORDS;
-    kth::CoopArgs x = coop_args(c, mine, d_out, d_status);
+    kth::CoopArgs x = coop_args(c, FSLOT_OFF, d_out, d_status);
     x.zero2 = head_slots ? head_slots : c->islots + HSLOT_OFF;
     x.zero2_words = HSLOT_WORDS;
-    x.pre = with_pre ? pre_set(c, c->fin_set) : nullptr;
-    x.pre_zero = pre_set(c, 1 - c->fin_set);
-    kth::k_finish<F32><<<c->fin_grid, kth::DENSE_BLK, FIN_DYN_LDS, c->stream>>>(a, x);
-    c->fin_set ^= 1;
+    x.pre = with_pre ? pre_words(c) : nullptr;
+    x.last = d_last(c);
+    kth::k_finish<F32><<<c->fin_grid, kth::DENSE_BLK, FIN_DYN_LDS, c->stream>>>(a, x, last);
 }
 
 template <bool F32>
@@ -527,7 +542,7 @@ int run_radix(kth_ctx *c, const int32_t *keys, int64_t n, int64_t k, int32_t *d_
         over_keys(a, keys, n);
         init_rank(a, n, k);
         ev_main(c);
-        launch_finish<F32>(c, a, d_out, d_status);
+        launch_finish<F32>(c, a, d_out, d_status, single_word<F32>(c, 1));
         ev_main(c);
         c->last_state = 1;
         return launch_check();
@@ -545,7 +560,8 @@ int run_radix(kth_ctx *c, const int32_t *keys, int64_t n, int64_t k, int32_t *d_
         launch_level<F32>(c, a, false, level_grid((u64)n, sparse_wg(c)));
     }
     a = ch.next(kth::ADV_PICK, Chain::IN);
-    kth::k_result<F32><<<1, kth::BLK, 0, c->stream>>>(a, d_out, d_status, c->islots, ISLOT_WORDS);
+    kth::k_result<F32><<<1, kth::BLK, 0, c->stream>>>(a, d_out, d_status, c->islots, ISLOT_WORDS, d_last(c),
+                                                     single_word<F32>(c, 1));
     c->last_state = 1;
     return launch_check();
 }
@@ -620,14 +636,14 @@ int run_window(kth_ctx *c, const int32_t *keys, int64_t n, int64_t k, int32_t *d
         a = ch.next(kth::ADV_CARRY, Chain::ACC);
         over_keys(a, keys, n);
         const bool pre = tflag == 0 && c->pre_hist;
-        if (pre) a.pre_hist = pre_set(c, c->fin_set);
+        if (pre) a.pre_hist = pre_words(c);
         ev_main(c);
         launch_main<F32>(c, a, tflag, tflags);
         ev_main(c);
         // decide + candidate (or fallback) levels + answer in one launch
         a = ch.next(kth::ADV_DECIDE, Chain::IN);
         over_keys(a, keys, n);
-        launch_finish<F32>(c, a, d_out, d_status, pre);
+        launch_finish<F32>(c, a, d_out, d_status, single_word<F32>(c, 0), pre);
         c->last_state = 0;
         c->counts_left = true;  // (k_head clears them; a sharded select on this ctx must too)
         return launch_check();
@@ -664,13 +680,17 @@ int run_window(kth_ctx *c, const int32_t *keys, int64_t n, int64_t k, int32_t *d
     a = ch.next(kth::ADV_PICK, Chain::IN);
     // k_result clears the slots and the candidate count for the next select --
     // but a top-k with candidate rows (tflag 3 / 4) still reads the count in
-    // k_topk_cands: there it clears the three slots only and the next select
-    // re-zeroes (dirty).  (It used to clear the count here too, and that top-k
-    // then missed the candidates' share: a bracket failure, nothing written.)
+    // k_topk_cands: there it clears the three slots only and the top-k clears
+    // the count itself, on the stream right after that kernel (count_kept).
+    // (It used to clear the count here too, and that top-k then missed the
+    // candidates' share: a bracket failure, nothing written.  Then the NEXT
+    // call cleared it, which a graph captured earlier does not do: its replay
+    // appended its candidates after the top-k's.)
     const bool keep_count = tflag == 3 || tflag == 4;
     kth::k_result<F32><<<1, kth::BLK, 0, c->stream>>>(a, d_out, d_status, c->islots,
-                                                     keep_count ? 3 * (u64)kth::STATS_WORDS : (u64)ISLOT_WORDS);
-    if (keep_count) c->dirty = true;
+                                                     keep_count ? 3 * (u64)kth::STATS_WORDS : (u64)ISLOT_WORDS,
+                                                     d_last(c), single_word<F32>(c, 1));
+    if (keep_count) c->count_kept = true;
     c->last_state = 1;
     return launch_check();
 }
@@ -687,11 +707,9 @@ void coop_tick(kth_ctx *c) {
 template <bool F32 = false>
 int select_enqueue(kth_ctx *c, const int32_t *d_keys, int64_t n, int64_t k, int32_t *d_out, int32_t *d_status,
                    int tflag = 0, uint32_t *tflags = nullptr) {
-    c->last_f32 = F32;
-    c->multi_last = c->last_k16 = false;
-    if (c->dirty) {
+    if (c->dirty || c->count_kept) {  // (count_kept: that top-k failed before its clear)
         HIP_TRY(hipMemsetAsync(c->islots, 0, SLOT_ALLOC_WORDS * sizeof(u64), c->stream));
-        c->dirty = false;
+        c->dirty = c->count_kept = false;
     }
     int rc;
     ev_mark(c, c->ev_total, c->total_used);
@@ -950,6 +968,7 @@ int kth_ctx_create(int device, kth_ctx **out) {
             break;
         }
         if (hipMemset(c->st, 0, 2 * sizeof(SelState)) != hipSuccess ||
+            hipMemset(c->d_status, 0, 4 * sizeof(int32_t)) != hipSuccess ||  // (LastCall: no selection yet)
             hipMemset(c->islots, 0, SLOT_ALLOC_WORDS * sizeof(u64)) != hipSuccess) {
             rc = KTH_EHIP;
             break;
@@ -1269,7 +1288,7 @@ int run_multi_window(kth_ctx *c, const int32_t *keys, int64_t n, const int64_t *
     for (int j = 0; j < D; ++j) {
         StepArgs a = chains[j].next(kth::ADV_DECIDE, Chain::IN);
         over_keys(a, keys, n);
-        launch_finish<F32>(c, a, outs[j], d_status ? d_status + 2 * j : nullptr, false, head_slots[j]);
+        launch_finish<F32>(c, a, outs[j], d_status ? d_status + 2 * j : nullptr, c->multi_tag, false, head_slots[j]);
     }
     return launch_check();
 }
@@ -1288,19 +1307,24 @@ int multi_async(kth_ctx *c, const int32_t *d_keys, int64_t n, const int64_t *ks,
     for (int j = 0; j < D; ++j) outs[j] = d_out ? d_out + first[j] : nullptr;
     int32_t *d_status = status ? c->d_mstatus : nullptr;
     int rc = KTH_OK;
+    // every final launch below leaves the call's LastCall word: the set of its last rank
+    // (multi_tag is set for the launches of this call only, whichever way it returns)
+    struct TagScope {
+        kth_ctx *c;
+        ~TagScope() { c->multi_tag = 0; }
+    } tag_scope{c};
+    c->multi_tag = c->multi_word = last_word(LAST_MULTI, F32, c->multi_set[m - 1]);
     // (one distinct rank is the single select: k_main<0> alone is HBM-bound,
     // 0.70 against 0.78 ms at 2^30 through k_main_multi)
     if (n > RADIX_MAX_N && c->coop && D > 1) {
-        if (c->dirty) {
+        if (c->dirty || c->count_kept) {
             HIP_TRY(hipMemsetAsync(c->islots, 0, SLOT_ALLOC_WORDS * sizeof(u64), c->stream));
-            c->dirty = false;
+            c->dirty = c->count_kept = false;
         }
         if (c->multi_dirty) {
             HIP_TRY(hipMemsetAsync(c->mslots.p, 0, c->mslots.count * sizeof(u64), c->stream));
             c->multi_dirty = false;
         }
-        c->last_f32 = F32;
-        c->last_k16 = false;
         c->multi_cap = cand_capacity(n);
         ev_mark(c, c->ev_total, c->total_used);
         rc = run_multi_window<F32>(c, d_keys, n, dk, D, outs, d_status);
@@ -1324,7 +1348,6 @@ int multi_async(kth_ctx *c, const int32_t *d_keys, int64_t n, const int64_t *ks,
             if (first[c->multi_set[i]] != i)
                 HIP_TRY(hipMemcpyAsync(d_out + i, d_out + first[c->multi_set[i]], sizeof(int32_t),
                                        hipMemcpyDeviceToDevice, c->stream));
-    c->multi_last = true;
     return KTH_OK;
 }
 
@@ -1453,6 +1476,8 @@ int run_k16(kth_ctx *c, const uint16_t *keys, int64_t n, const int64_t *dk, int 
         if (!small) window_ranks(n, dk[j], s, &pa.rlo[j], &pa.rhi[j]);
     }
     pa.out = out;
+    pa.last = d_last(c);
+    pa.last_word = c->multi_word = last_word(LAST_K16, false, c->multi_set[out.m - 1], kind);
     kth::k16_pick<<<1, kth::K16_HIST_BLK, 0, c->stream>>>(pa);
     if (!small) {
         const kth::K16Args ma{keys, (u64)n, D, nl2, top2, c->k16st.p, bins};
@@ -1480,9 +1505,6 @@ int k16_async(kth_ctx *c, const uint16_t *d_keys, int64_t n, const int64_t *ks, 
         HIP_TRY(hipMemsetAsync(c->k16.p, 0, c->k16.count * sizeof(u64), c->stream));
         c->k16_dirty = false;
     }
-    c->last_k16 = true;
-    c->multi_last = false;
-    c->k16_kind = kind;
     kth::K16Out out;
     memset(&out, 0, sizeof out);
     out.m = m;
@@ -1630,8 +1652,17 @@ int kth_ctx_coop(const kth_ctx *c) {
 
 namespace {
 
+// The ctx's LastCall word, read from the device (synchronises the ctx stream).
+int fetch_last(kth_ctx *c, LastCall *last) {
+    KTH_TRY(set_device(c));
+    HIP_TRY(hipMemcpyAsync(c->h_status + 2, d_last(c), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *last = last_of_word((uint32_t)c->h_status[2]);
+    return KTH_OK;
+}
+
 // A selection state on the device as kth_stats (synchronises the ctx stream).
-int fetch_stats(kth_ctx *c, const SelState *d_state, u64 capacity, kth_stats *out) {
+int fetch_stats(kth_ctx *c, const SelState *d_state, u64 capacity, bool f32, kth_stats *out) {
     KTH_TRY(set_device(c));
     HIP_TRY(hipMemcpyAsync(c->h_state, d_state, sizeof(SelState), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1648,13 +1679,13 @@ int fetch_stats(kth_ctx *c, const SelState *d_state, u64 capacity, kth_stats *ou
     out->cnt_eq_hi = s.cnt[kth::C_EQHI];
     out->candidates = s.cnt[kth::C_IN];
     out->capacity = capacity;
-    out->answer = c->last_f32 ? (int32_t)kth::f32_of_key(s.answer) : (int32_t)(s.answer ^ 0x80000000u);
+    out->answer = f32 ? (int32_t)kth::f32_of_key(s.answer) : (int32_t)(s.answer ^ 0x80000000u);
     out->error = (int32_t)s.error;
     return KTH_OK;
 }
 
-// Rank set j of the last 16-bit call: the window as order keys, the answer's bits.
-int fetch_stats_k16(kth_ctx *c, int j, kth_stats *out) {
+// Rank set j of the last 16-bit call (keys of `kind`): the window as order keys, the answer's bits.
+int fetch_stats_k16(kth_ctx *c, int j, int kind, kth_stats *out) {
     KTH_TRY(set_device(c));
     kth::K16State *h = reinterpret_cast<kth::K16State *>(c->h_state);
     static_assert(sizeof(kth::K16State) <= sizeof(SelState), "the pinned state buffer holds either");
@@ -1663,22 +1694,40 @@ int fetch_stats_k16(kth_ctx *c, int j, kth_stats *out) {
     memset(out, 0, sizeof *out);
     out->path = (int32_t)h->path;
     out->mode = (int32_t)h->mode;
-    out->lo_key = kth::k16_key_of_ord(h->lo, c->k16_kind);
-    out->hi_key = kth::k16_key_of_ord(h->hi, c->k16_kind);
+    out->lo_key = kth::k16_key_of_ord(h->lo, kind);
+    out->hi_key = kth::k16_key_of_ord(h->hi, kind);
     out->n = h->n;
     out->k = h->k;
     out->cnt_lt = h->cnt_lt;
     out->candidates = h->inside;
-    out->answer = (int32_t)kth::k16_bits_of_ord(h->answer, c->k16_kind);
+    out->answer = (int32_t)kth::k16_bits_of_ord(h->answer, kind);
     out->error = (int32_t)h->error;
     return KTH_OK;
 }
 
-// rank i of the last multi call: its final state is state 0 of its set
+// The final state LastCall names.
+int last_stats(kth_ctx *c, const LastCall &last, kth_stats *out) {
+    switch (last.form) {
+    case LAST_K16: return fetch_stats_k16(c, last.index, last.k16_kind, out);
+    case LAST_MULTI: return fetch_stats(c, c->mstate.p + 2 * (size_t)last.index, c->multi_cap, last.f32, out);
+    case LAST_SINGLE: return fetch_stats(c, c->st + (last.index & 1), c->cand.count, last.f32, out);
+    default: return KTH_EINVAL;  // no selection yet
+    }
+}
+
+// Rank i of the multi or 16-bit call that ran last: the state of its set, a
+// multi call's state 0.  The map from i to a set is the host's record of the
+// last such call enqueued or captured here, so it serves only while what ran
+// last on the device is a call of that form and key kind: KTH_EINVAL after a
+// single select or a call of another kind (a replayed graph, for instance).
 int multi_stats(kth_ctx *c, int i, kth_stats *out) {
     if (!c || !out || i < 0 || i >= c->multi_m) return KTH_EINVAL;
-    if (c->last_k16) return fetch_stats_k16(c, c->multi_set[i], out);
-    return fetch_stats(c, c->mstate.p + 2 * (size_t)c->multi_set[i], c->multi_cap, out);
+    LastCall last;
+    KTH_TRY(fetch_last(c, &last));
+    const LastCall mine = last_of_word(c->multi_word);
+    if (last.form != mine.form || last.f32 != mine.f32 || last.k16_kind != mine.k16_kind) return KTH_EINVAL;
+    last.index = c->multi_set[i];
+    return last_stats(c, last, out);
 }
 
 }  // namespace
@@ -1689,9 +1738,9 @@ int kth_ctx_multi_stats(kth_ctx *c, int i, kth_stats *out) { return multi_stats(
 
 int kth_ctx_last_stats(kth_ctx *c, kth_stats *out) {
     if (!c || !out) return KTH_EINVAL;
-    if (c->multi_last || c->last_k16) return multi_stats(c, c->multi_m - 1, out);
-    if (c->last_state < 0) return KTH_EINVAL;
-    return fetch_stats(c, c->st + c->last_state, c->cand.count, out);
+    LastCall last;
+    KTH_TRY(fetch_last(c, &last));
+    return last_stats(c, last, out);
 }
 
 int kth_ctx_enable_timing(kth_ctx *c, int on) {
@@ -1847,6 +1896,10 @@ int topk_impl(kth_ctx *c, const int32_t *d_keys, int64_t n, int64_t k, int large
         HIP_TRY(hipMemsetAsync(tcnt, 0, ntiles * 4, c->stream));
         kth::k_topk_cands<<<c->num_cu * 8, kth::TK_BLOCK, 0, c->stream>>>(
             c->cand.p, c->cand_rows.p, cand_count(c), c->cand.count, c->d_status, flip, tcnt, tflags, sel_st);
+        if (c->count_kept) {  // the per-level select left the count for the kernel above: nothing reads it now
+            HIP_TRY(hipMemsetAsync(cand_count(c), 0, sizeof(u64), c->stream));
+            c->count_kept = false;
+        }
         kth::k_topk_count<true, 1, F32><<<g, kth::TK_BLOCK, 0, c->stream>>>(
             keys, (u64)n, ntiles, c->d_status, flip, tcnt, tflags, head, nfull, sel_st, ncov, rwl);
     } else if (aligned) {
@@ -1947,9 +2000,9 @@ int kth_dist_begin(kth_ctx *c, uint64_t *d_slots, int64_t n_total, int64_t k) {
     // count slot and candidate count for its next k_head to clear (the
     // streaming pass would append after a stale count, and the candidate
     // levels would histogram the previous select's keys)
-    if (c->dirty || c->dist_open || c->counts_left)
+    if (c->dirty || c->dist_open || c->counts_left || c->count_kept)
         HIP_TRY(hipMemsetAsync(c->islots, 0, SLOT_ALLOC_WORDS * sizeof(u64), c->stream));
-    c->dirty = false;
+    c->dirty = c->count_kept = false;
     c->counts_left = false;
     c->dist_open = true;
     return KTH_OK;
@@ -2133,11 +2186,11 @@ static int launch_dresult(kth_ctx *c, int L, int32_t *d_out, uint32_t early) {
     StepArgs a = Chain{c, c->uslots, L}.next(kth::ADV_PICK, Chain::IN);
     // (the islots and, right after them, k_head's slots of a cooperative window)
     static_assert(ISLOT_WORDS % 2 == 0, "k_dresult zeroes 16-byte words from the islots on");
+    // (the sharded protocol is int32 only)
     kth::k_dresult<kth::BLK><<<16, kth::BLK, 0, c->stream>>>(a, d_out, c->d_status, c->islots,
-                                                            ISLOT_WORDS + HSLOT_WORDS, early);
+                                                            ISLOT_WORDS + HSLOT_WORDS, early, d_last(c),
+                                                            last_word(LAST_SINGLE, false, L % 2));
     c->last_state = L % 2;
-    c->last_f32 = false;  // (the sharded protocol is int32 only)
-    c->multi_last = c->last_k16 = false;
     return launch_check();
 }
 

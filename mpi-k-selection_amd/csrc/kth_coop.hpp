@@ -35,8 +35,8 @@ struct CoopArgs {
     uint32_t *tail;    // k_finish: FIN_LDS_KEYS keys of the last bin (finish_tail)
     uint32_t sample_ready;  // k_head: the sample (order keys) is already in `sample` (sharded window)
     uint32_t fault;    // test hook (KTH_HOOK_FAULT_BARRIER): the grid barriers and the tail wait report a timeout
-    const uint32_t *pre;  // k_finish: k_main<0>'s first candidate digit (PreHist), or null
-    uint32_t *pre_zero;   // k_finish: the other PreHist set, cleared for the next select
+    uint32_t *pre;     // k_finish: k_main<0>'s first candidate digit (PreHist), or null; cleared before the launch ends
+    uint32_t *last;    // k_finish: the ctx's last-call word (kth_ctx_last_stats), which gets the launch's tag
 };
 
 // The dense first digit of k_finish (nb <= NBINS / copies bins) is flushed
@@ -226,10 +226,18 @@ __global__ __launch_bounds__(DENSE_BLK) void k_head(StepArgs a, CoopArgs x, cons
 //     (x.pre, PreHist: complete unless a workgroup flushed its staging
 //     mid-pass), it is picked from there: no histogram, flush or barrier.  The later digits only see the keys of one bin, and
 //     once that bin fits one workgroup's LDS, finish_tail ends the launch.
-//   * Slots come in two sets used by alternate launches (x.slots: this
-//     launch's, a.stats_zero: the other set, cleared here for the next one),
-//     and the sample phase's slots (x.zero2) are cleared here too: no barrier
-//     after the last level.
+//   * The launch leaves what it used zero: its slots (x.slots), k_main<0>'s
+//     PreHist (x.pre) and the sample phase's slots (x.zero2), so the same
+//     launch can run again as enqueued (a replayed graph) after any other.
+//     A slot or PreHist may only be cleared once every workgroup has picked
+//     from it.  The levels below the last are behind a grid barrier already.
+//     For the last one the tail's arrival count serves: the workgroup that
+//     finishes alone arrives last, so it clears the last level's slot and
+//     PreHist -- no barrier after the last level.  Only a launch that ends
+//     without a tail (heavy ties, the fallback over the input) pays one more
+//     grid barrier before the clear.  (Until graphs were replayed, two sets
+//     alternated, each launch clearing the other: the host chose the set by
+//     its call parity, which a graph freezes.)
 constexpr int FIN_LDS_KEYS = 32768;  // LDS-resident keys per workgroup (128 KiB of dynamic LDS)
 constexpr int FIN_UNROLL = 4;        // 16-B loads in flight per thread (1024-thread workgroups: <= 128 VGPRs)
 
@@ -493,8 +501,9 @@ __device__ bool finish_tail(const StepArgs &a, SelState &ss, const CoopArgs &x, 
 // F32: a.keys holds float32 words.  The input is only read after a window miss
 // or on the radix path (MODE_FULL); its words become ordered words as they are
 // loaded, so the LDS slice, the tail and every later digit see the int32 form.
+// last_tag: what the writer leaves in *x.last (kth_api.hip LastCall).
 template <bool F32 = false>
-__global__ __launch_bounds__(DENSE_BLK) void k_finish(StepArgs a, CoopArgs x) {
+__global__ __launch_bounds__(DENSE_BLK) void k_finish(StepArgs a, CoopArgs x, uint32_t last_tag) {
     __shared__ SelState ss;
     __shared__ u64 scratch[2 * (DENSE_BLK / WAVE) + 8];
     __shared__ __attribute__((aligned(16))) uint32_t lh[2][NBINS];
@@ -527,9 +536,11 @@ __global__ __launch_bounds__(DENSE_BLK) void k_finish(StepArgs a, CoopArgs x) {
         nk = min(per, count - b0);
     }
     bool ok = true, tail = false;
+    int levels = 0;  // levels run (block-uniform)
     for (int L = 0; L < FIN_LEVELS; ++L) {
         const uint32_t mode = ss.mode;
         if (mode != MODE_CAND && mode != MODE_FULL) break;  // block-uniform
+        levels = L + 1;
         bool share;
         const HistPlan plan = make_plan(ss, &share);
         if (L > 0) {
@@ -646,6 +657,8 @@ __global__ __launch_bounds__(DENSE_BLK) void k_finish(StepArgs a, CoopArgs x) {
             break;
         }
     }
+    // no tail: every workgroup has picked the last level before its slot and PreHist are cleared below
+    if (levels > 0 && !tail) grid_sync(gb, s_base, ok);
     grid_bar_finish(gb, s_base);
     bool writer = blockIdx.x == 0;
     if (tail) {
@@ -665,15 +678,31 @@ __global__ __launch_bounds__(DENSE_BLK) void k_finish(StepArgs a, CoopArgs x) {
             x.d_status[0] = i32_of_key(o.answer);
             x.d_status[1] = (int32_t)o.error;
         }
+        if (x.last) *x.last = last_tag;
     }
-    // the other slot set and the sample phase's slots, for the next select
-    for (u64 i = (u64)blockIdx.x * DENSE_BLK + threadIdx.x; i < a.zero_words; i += (u64)gridDim.x * DENSE_BLK)
-        a.stats_zero[i] = 0;
-    for (u64 i = (u64)blockIdx.x * DENSE_BLK + threadIdx.x; i < x.zero2_words; i += (u64)gridDim.x * DENSE_BLK)
-        x.zero2[i] = 0;
-    if (x.pre_zero)
-        for (u64 i = (u64)blockIdx.x * DENSE_BLK + threadIdx.x; i < (u64)PRE_WORDS; i += (u64)gridDim.x * DENSE_BLK)
-            x.pre_zero[i] = 0u;
+    // What this launch used is zero again when it ends (see the head of this
+    // section).  With a tail, only the finisher -- the last to arrive, so the
+    // others have picked -- may clear the last level's slot and PreHist; the
+    // slots below it lie behind that level's grid barrier (a level picked
+    // from PreHist has none, and flushed into no slot).  Without one, every
+    // workgroup is past the barrier above, or no level ran: then no slot was
+    // added into, and PreHist (k_main<0> fills it whatever this launch
+    // decides) is read by no pick.
+    const u64 spread = (u64)blockIdx.x * DENSE_BLK + threadIdx.x, step = (u64)gridDim.x * DENSE_BLK;
+    const u64 shared_words = (u64)(tail ? levels - 1 : levels) * STATS_WORDS;
+    for (u64 i = spread; i < shared_words; i += step) x.slots[i] = 0;
+    for (u64 i = spread; i < x.zero2_words; i += step) x.zero2[i] = 0;
+    if (tail) {
+        if (writer) {  // block-uniform
+            if (!(levels == 1 && use_pre))
+                for (uint32_t i = threadIdx.x; i < (uint32_t)STATS_WORDS; i += DENSE_BLK) x.slots[shared_words + i] = 0;
+            if (x.pre)
+                for (uint32_t i = threadIdx.x; i < (uint32_t)PRE_WORDS / 4; i += DENSE_BLK)
+                    reinterpret_cast<uint4 *>(x.pre)[i] = make_uint4(0, 0, 0, 0);
+        }
+    } else if (x.pre) {
+        for (u64 i = spread; i < (u64)PRE_WORDS; i += step) x.pre[i] = 0u;
+    }
     KTH_STAMP(a, 7);
 }
 

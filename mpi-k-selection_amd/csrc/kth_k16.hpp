@@ -248,6 +248,8 @@ struct K16PickArgs {
     uint32_t C, top;
     u64 k[MULTI_MAX], rlo[MULTI_MAX], rhi[MULTI_MAX];
     K16Out out;
+    uint32_t *last;       // the ctx's last-call word (kth_ctx_last_stats) ...
+    uint32_t last_word;   // ... and what this call leaves there
 };
 __global__ __launch_bounds__(K16_HIST_BLK) void k16_pick(K16PickArgs a) {
     constexpr int PER = K16_VALUES / K16_HIST_BLK;  // 64 bins a thread: a wave reads them with one load
@@ -320,6 +322,7 @@ __global__ __launch_bounds__(K16_HIST_BLK) void k16_pick(K16PickArgs a) {
         a.st[j] = s;
         if (a.small) k16_publish(a.out, j, s);
     }
+    if (threadIdx.x == 0 && a.last) *a.last = a.last_word;
 }
 
 // ------------------------------------------------------------------ k16_main

@@ -105,7 +105,7 @@ __host__ __device__ __forceinline__ uint32_t fin_first_digit(uint32_t W) {
 // workgroup then reports in `incomplete` instead), into PRE_COPIES copies
 // (workgroup b adds to copy b % PRE_COPIES: 256 same-address adders a bin, not
 // 1024, and they finish over the pass's ~80 us of workgroup end times).  k_finish picks the digit from it without a histogram pass, a flush
-// or a grid barrier.  Two sets, alternate selects (k_finish clears the other).
+// or a grid barrier, and clears it before its launch ends.
 #ifndef KTH_PRE_COPIES
 #define KTH_PRE_COPIES 4
 #endif
@@ -1532,10 +1532,12 @@ __global__ __launch_bounds__(BLK) void k_main(StepArgs a, uint32_t *__restrict__
 // Final digit: one workgroup.  Writes the answer and the error word, then
 // zeroes the ctx-internal slots (and local candidate count) for the next call.
 // d_out takes the caller's word (F32: float bits); d_status[0] stays the
-// ordered word, which the top-k kernels compare against.
+// ordered word, which the top-k kernels compare against.  *last takes last_word
+// (the ctx's last-call word, kth_ctx_last_stats), here and in the other kernels
+// that end a selection.
 template <bool F32 = false>
 __global__ __launch_bounds__(BLK) void k_result(StepArgs a, int32_t *d_out, int32_t *d_status, u64 *izero,
-                                                u64 izero_words) {
+                                                u64 izero_words, uint32_t *last, uint32_t last_word) {
     __shared__ SelState ss;
     __shared__ u64 scratch[2 * (BLK / WAVE) + 8];
     KTH_STAMP(a, 0);
@@ -1549,6 +1551,7 @@ __global__ __launch_bounds__(BLK) void k_result(StepArgs a, int32_t *d_out, int3
             d_status[0] = i32_of_key(o.answer);
             d_status[1] = (int32_t)o.error;
         }
+        if (last) *last = last_word;
     }
     __syncthreads();
     for (u64 i = threadIdx.x; i < izero_words; i += BLK) izero[i] = 0;
@@ -1807,7 +1810,7 @@ template <int BLOCK>
 // still live (more digits to come, no error) nothing is written or cleared --
 // the protocol then goes on and its final k_dresult does the work.
 __global__ __launch_bounds__(BLOCK) void k_dresult(StepArgs a, int32_t *d_out, int32_t *d_status, u64 *izero,
-                                                   u64 izero_words, uint32_t early) {
+                                                   u64 izero_words, uint32_t early, uint32_t *last, uint32_t last_word) {
     __shared__ SelState ss;
     __shared__ u64 scratch[2 * (BLOCK / WAVE) + 8];
     __shared__ u64 cnts[NCOUNTS];
@@ -1829,6 +1832,7 @@ __global__ __launch_bounds__(BLOCK) void k_dresult(StepArgs a, int32_t *d_out, i
                 d_status[0] = i32_of_key(o.answer);
                 d_status[1] = (int32_t)o.error;
             }
+            if (last) *last = last_word;
         }
     }
     // (izero is 16-byte aligned; an odd word count leaves one u64)
@@ -1841,7 +1845,8 @@ __global__ __launch_bounds__(BLOCK) void k_dresult(StepArgs a, int32_t *d_out, i
 // n <= 16384: whole selection in one workgroup, keys in LDS.
 template <bool F32 = false>
 __global__ __launch_bounds__(SMALL_BLOCK) void k_small(const int32_t *__restrict__ keys, u64 n, u64 k,
-                                                       int32_t *d_out, int32_t *d_status, SelState *st_out) {
+                                                       int32_t *d_out, int32_t *d_status, SelState *st_out,
+                                                       uint32_t *last, uint32_t last_word) {
     extern __shared__ __attribute__((aligned(16))) uint32_t skeys[];
     __shared__ uint32_t hist[NBINS];
     __shared__ u64 scratch[SMALL_BLOCK / WAVE + 4];
@@ -1885,6 +1890,7 @@ __global__ __launch_bounds__(SMALL_BLOCK) void k_small(const int32_t *__restrict
             o.hi = 0xFFFFFFFFu;
             *st_out = o;
         }
+        if (last) *last = last_word;
     }
 }
 

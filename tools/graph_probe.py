@@ -3,7 +3,8 @@ stream, eagerly on the null stream, and replayed from one captured HIP graph
 (torch.cuda.CUDAGraph over kth_select_i32_async on the ctx stream), the three
 interleaved round by round after a long warmup.  Prints ms per select for each
 and whether every answer agrees.  Design probe, not part of the product.
-Usage: python tools/graph_probe.py [log2n=30] [reps=20] [rounds=6] [order=eager,null,graph]"""
+Usage: python tools/graph_probe.py [log2n=30] [reps=40] [rounds=6] [order=eager,null,graph]
+(reps: selects per round and per graph; any count, odd or even)"""
 import os
 import sys
 import time
@@ -16,7 +17,7 @@ import kselect  # noqa: E402
 
 def main():
     log2n = int(sys.argv[1]) if len(sys.argv) > 1 else 30
-    reps = int(sys.argv[2]) if len(sys.argv) > 2 else 20
+    reps = int(sys.argv[2]) if len(sys.argv) > 2 else 40
     rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 6
     order = sys.argv[4].split(",") if len(sys.argv) > 4 else ["eager", "null", "graph"]
     n, k = 1 << log2n, 1 << (log2n - 1)
@@ -26,10 +27,10 @@ def main():
     keys = torch.empty(n, dtype=torch.int32, device=dev)
     sel.fill(keys, n, kselect.FAMILIES["uniform_half"], 12345)
     sel.reserve(n)
-    outs = {m: torch.zeros(2 * reps, dtype=torch.int32, device=dev) for m in ("eager", "null", "graph")}
+    outs = {m: torch.zeros(reps, dtype=torch.int32, device=dev) for m in ("eager", "null", "graph")}
 
     def eager(out):
-        for i in range(2 * reps):  # an even count: the ctx's alternating slot sets come back to the start
+        for i in range(reps):
             sel.select_async(keys, n, k, out[i:i + 1])
 
     torch.cuda.synchronize()
@@ -54,7 +55,7 @@ def main():
                 with torch.cuda.stream(s):
                     eager(outs[m])
             torch.cuda.synchronize()
-            res.setdefault(m, []).append((time.perf_counter() - t0) * 1e3 / (2 * reps))
+            res.setdefault(m, []).append((time.perf_counter() - t0) * 1e3 / reps)
     ans = {m: o.cpu().tolist() for m, o in outs.items()}
     ok = len(set(ans["eager"])) == 1 and all(ans[m] == ans["eager"] for m in order)
     for m, v in res.items():
