@@ -265,6 +265,26 @@ int kth_ctx_reserve_k16(kth_ctx *ctx, int64_t n, int m);
 /* Stats of the last select on this ctx (synchronises the ctx stream). */
 int kth_ctx_last_stats(kth_ctx *ctx, kth_stats *st);
 
+/* How the cooperative finish (k_finish) of the last select on this ctx ended,
+ * read from the last-call word its final kernel leaves (synchronises the ctx
+ * stream; follows a replayed graph like kth_ctx_last_stats):
+ *   KTH_FINISH_NONE     the last selection ended in another kernel (LDS path,
+ *                       per-level path, 16-bit keys)
+ *   KTH_FINISH_COUNTS   decided from the streaming pass's counts, no level ran
+ *   KTH_FINISH_SLICES   every workgroup scanned its slice of the domain and the
+ *                       last to arrive resolved the picked bin (the slice tail)
+ *   KTH_FINISH_GROUPED  one workgroup gathered the picked bin from the grouped
+ *                       candidates by k_main<0>'s directory
+ *   KTH_FINISH_LEVELS   grid-wide levels to the end, no tail (heavy ties, the
+ *                       fallback over the input)
+ * KTH_EINVAL before the first selection. */
+#define KTH_FINISH_NONE 0
+#define KTH_FINISH_COUNTS 1
+#define KTH_FINISH_SLICES 2
+#define KTH_FINISH_GROUPED 3
+#define KTH_FINISH_LEVELS 4
+int kth_ctx_last_finish_form(kth_ctx *ctx, int *form);
+
 /* Diagnostics: 1 when the ctx runs the cooperative (grid-barrier) kernels,
  * 0 while it is on the per-level path -- for COOP_BACKOFF = 64 selections of
  * any entry point after a grid-barrier timeout (the synchronous entry points
@@ -285,11 +305,15 @@ int kth_ctx_coop(const kth_ctx *ctx);
  *   KTH_HOOK_K16_MISS         value != 0: the sample phase of the 16-bit select
  *                             publishes a window that holds no key, so the
  *                             later passes must produce every answer
+ *   KTH_HOOK_FINISH_SLICES    value != 0: k_finish ignores the group directory
+ *                             and takes the slice tail (the grouped form's
+ *                             reference); frozen in a captured graph
  * Returns KTH_EINVAL for an unknown hook or a bad value. */
 #define KTH_HOOK_FAULT_TOPK_RANK 1
 #define KTH_HOOK_FAULT_BARRIER 2
 #define KTH_HOOK_TOPK_SEG_CAP 3
 #define KTH_HOOK_K16_MISS 4
+#define KTH_HOOK_FINISH_SLICES 5
 int kth_ctx_test_hook(kth_ctx *ctx, int hook, int64_t value);
 
 /* --- timing (bench) ----------------------------------------------------------

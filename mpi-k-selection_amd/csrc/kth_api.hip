@@ -157,6 +157,8 @@ struct kth_ctx {
     uint32_t head_slack64 = (uint32_t)(HEAD_SLACK * 64);
     uint32_t head_abs_div = 1024;  // plain select: early-window floor s / head_abs_div sample keys (KTH_HEAD_ABS; 0 = off)
     bool pre_hist = true;      // k_main<0> histograms the candidates' first digit for k_finish (KTH_PRE_HIST=0: off)
+    bool group = true;         // ... and writes them grouped by it, with a directory, for k_finish's gather (KTH_GROUP=0: off)
+    bool finish_slices = false;  // KTH_HOOK_FINISH_SLICES (tests): k_finish ignores the directory and takes the slice tail
     hipStream_t stream = nullptr;
     bool own_stream = false;
     int num_cu = 256;
@@ -164,6 +166,7 @@ struct kth_ctx {
     u64 *islots = nullptr;    // ISLOT_WORDS
     DevBuf<uint32_t> sample;
     DevBuf<uint32_t> cand;
+    DevBuf<uint32_t> gdir;       // k_main<0>'s group directory: a row per workgroup (single-GPU window path)
     DevBuf<uint32_t> cand_rows;  // k_main<3/4>: each candidate's 1024-key row (top-k)
     // k_main<5/6> (top-k): per-wave segments of staged keys + positions, per wave-row counts
     DevBuf<int32_t> tk_segv;
@@ -270,9 +273,17 @@ int reserve_cand(kth_ctx *c, int64_t n, bool rows = false) {
     return rows ? c->cand_rows.reserve(c->cand.count) : KTH_OK;
 }
 
-// The window path's scratch: the sample and the candidates.
+// Is the plain pass's group directory in use, and its words (a row per
+// workgroup of the larger of k_main<0>'s two grids)?
+bool grouping(const kth_ctx *c) { return c->coop && c->pre_hist && c->group; }
+u64 gdir_words(const kth_ctx *c) {
+    return (u64)std::max(c->main_grid[0][0], c->main_grid[1][0]) * (kth::GDIR_ROW_BYTES / 4);
+}
+
+// The window path's scratch: the sample, the candidates and the group directory.
 int reserve_window(kth_ctx *c, int64_t n) {
     KTH_TRY(c->sample.reserve((u64)sample_size(n)));
+    if (grouping(c)) KTH_TRY(c->gdir.reserve(gdir_words(c)));
     return reserve_cand(c, n);
 }
 
@@ -524,15 +535,19 @@ uint32_t *pre_words(kth_ctx *c) { return reinterpret_cast<uint32_t *>(c->islots 
 // last: the LastCall word the launch leaves
 // with_pre: this select's k_main<0> histogrammed the candidates' first digit into PreHist
 // head_slots: the sample phase's slots this launch clears (null: the ctx's own)
+// group_rows: ... and wrote the candidates grouped, a directory row for each of this many workgroups (0: not)
 template <bool F32>
 void launch_finish(kth_ctx *c, const StepArgs &a, int32_t *d_out, int32_t *d_status, uint32_t last, bool with_pre = false,
-                   u64 *head_slots = nullptr) {
+                   u64 *head_slots = nullptr, int group_rows = 0) {
     kth::CoopArgs x = coop_args(c, FSLOT_OFF, d_out, d_status);
     x.zero2 = head_slots ? head_slots : c->islots + HSLOT_OFF;
     x.zero2_words = HSLOT_WORDS;
     x.pre = with_pre ? pre_words(c) : nullptr;
     x.last = d_last(c);
-    kth::k_finish<F32><<<c->fin_grid, kth::DENSE_BLK, FIN_DYN_LDS, c->stream>>>(a, x, last);
+    kth::FinGroup fg{nullptr, 0u};
+    if (with_pre && group_rows > 0 && !c->finish_slices)
+        fg = kth::FinGroup{reinterpret_cast<const uint8_t *>(c->gdir.p), (uint32_t)group_rows};
+    kth::k_finish<F32><<<c->fin_grid, kth::DENSE_BLK, FIN_DYN_LDS, c->stream>>>(a, x, last, fg);
 }
 
 template <bool F32>
@@ -579,8 +594,9 @@ StepArgs head_step(Chain &ch, int64_t n, int64_t k, int64_t s, u64 r_lo, u64 r_h
 }
 
 // The streaming pass, plain (tflag 0) or with the top-k records of k_main<tflag>.
+// gdir: the plain pass (tflag 0) writes its candidates grouped and a row per workgroup here (null: not)
 template <bool F32>
-void launch_main(kth_ctx *c, const StepArgs &a, int tflag, uint32_t *tflags) {
+void launch_main(kth_ctx *c, const StepArgs &a, int tflag, uint32_t *tflags, uint32_t *gdir = nullptr) {
     const kth::TkSeg none{};
     // (the staged variants 5 / 6 exist for int32 keys only, and kth_topk_f32
     // never asks for them; a float32 pass that did would run plain)
@@ -598,7 +614,7 @@ void launch_main(kth_ctx *c, const StepArgs &a, int tflag, uint32_t *tflags) {
     case 6:
         if constexpr (!F32) kth::k_main<6><<<g, kth::BLK, 0, c->stream>>>(a, cand, tflags, nullptr, c->tk_seg);
         break;
-    default: kth::k_main<0, F32><<<g, kth::BLK, 0, c->stream>>>(a, cand, nullptr, nullptr, none); break;
+    default: kth::k_main<0, F32><<<g, kth::BLK, 0, c->stream>>>(a, cand, gdir, nullptr, none); break;
     }
 }
 
@@ -637,13 +653,14 @@ int run_window(kth_ctx *c, const int32_t *keys, int64_t n, int64_t k, int32_t *d
         over_keys(a, keys, n);
         const bool pre = tflag == 0 && c->pre_hist;
         if (pre) a.pre_hist = pre_words(c);
+        const bool grp = pre && grouping(c) && c->gdir.p != nullptr;
         ev_main(c);
-        launch_main<F32>(c, a, tflag, tflags);
+        launch_main<F32>(c, a, tflag, tflags, grp ? c->gdir.p : nullptr);
         ev_main(c);
         // decide + candidate (or fallback) levels + answer in one launch
         a = ch.next(kth::ADV_DECIDE, Chain::IN);
         over_keys(a, keys, n);
-        launch_finish<F32>(c, a, d_out, d_status, single_word<F32>(c, 0), pre);
+        launch_finish<F32>(c, a, d_out, d_status, single_word<F32>(c, 0), pre, nullptr, grp ? c->main_grid[F32][0] : 0);
         c->last_state = 0;
         c->counts_left = true;  // (k_head clears them; a sharded select on this ctx must too)
         return launch_check();
@@ -819,6 +836,7 @@ void read_tuning(kth_ctx *c) {
     if (const char *g = getenv("KTH_POST_SPARSE_GRID")) c->post_sparse_grid = std::max(1, atoi(g));
     if (const char *g = getenv("KTH_COOP")) c->coop = atoi(g) != 0;
     if (const char *g = getenv("KTH_PRE_HIST")) c->pre_hist = atoi(g) != 0;
+    if (const char *g = getenv("KTH_GROUP")) c->group = atoi(g) != 0;
     c->fin_grid = c->num_cu;
     if (const char *g = getenv("KTH_FIN_GRID")) c->fin_grid = std::max(1, std::min(atoi(g), c->num_cu));
     if (const char *g = getenv("KTH_HEAD_SLACK")) c->head_slack64 = (uint32_t)std::max(0.0, atof(g) * 64.0);
@@ -1029,6 +1047,7 @@ int kth_ctx_test_hook(kth_ctx *c, int hook, int64_t value) {
         c->topk_seg_cap = (u64)value;
         return KTH_OK;
     case KTH_HOOK_K16_MISS: c->k16_miss = value != 0; return KTH_OK;
+    case KTH_HOOK_FINISH_SLICES: c->finish_slices = value != 0; return KTH_OK;
     default: return KTH_EINVAL;
     }
 }
@@ -1041,7 +1060,7 @@ int kth_ctx_destroy(kth_ctx *c) {
     for (hipEvent_t e : c->ev_total) (void)hipEventDestroy(e);
     if (c->st) (void)hipFree(c->st);
     if (c->islots) (void)hipFree(c->islots);
-    release_all(c->sample, c->cand, c->cand_rows, c->tk_segv, c->tk_segp, c->tk_wcnt, c->tk_wstart, c->staging,
+    release_all(c->sample, c->cand, c->gdir, c->cand_rows, c->tk_segv, c->tk_segp, c->tk_wcnt, c->tk_wstart, c->staging,
                 c->topk, c->mstate, c->mslots, c->mcand, c->k16, c->k16st);
     if (c->d_mstatus) (void)hipFree(c->d_mstatus);
     if (c->h_mstatus) (void)hipHostFree(c->h_mstatus);
@@ -1741,6 +1760,15 @@ int kth_ctx_last_stats(kth_ctx *c, kth_stats *out) {
     LastCall last;
     KTH_TRY(fetch_last(c, &last));
     return last_stats(c, last, out);
+}
+
+int kth_ctx_last_finish_form(kth_ctx *c, int *form) {
+    if (!c || !form) return KTH_EINVAL;
+    LastCall last;
+    KTH_TRY(fetch_last(c, &last));
+    if (last.form == LAST_NONE) return KTH_EINVAL;  // no selection yet
+    *form = (int)((uint32_t)c->h_status[2] >> kth::LAST_FORM_SHIFT & 7u);
+    return KTH_OK;
 }
 
 int kth_ctx_enable_timing(kth_ctx *c, int on) {

@@ -13,7 +13,10 @@
 //             barrier -> pick; publishes the window for k_main (ADV_CARRY)
 //   k_finish  decide from k_main's counts -> per level: histogram the
 //             candidates (or, after a window miss, the input) -> barrier ->
-//             pick; writes the answer and leaves every slot zeroed
+//             pick; writes the answer and leaves every slot zeroed.  In the
+//             common case no level runs at all: the first digit comes from
+//             k_main<0>'s PreHist and one workgroup gathers the picked bin
+//             from the grouped candidates (finish_gather)
 // Both grids are small enough to be co-resident (one workgroup per CU at
 // most); the barrier is hierarchical (8 group counters, then one top counter:
 // same-address atomics serialise) and sense-reversing (the last arrivers reset
@@ -66,11 +69,14 @@ __device__ __forceinline__ void pick_slot_copies(SelState &ss, const u64 *slot, 
 
 // The first candidate digit from k_main<0>'s PreHist (nb <= PRE_BINS bins in
 // PRE_COPIES copies; written by the previous kernel: plain loads), summed per
-// bin, and picked (target 0).
+// bin, and picked (target 0).  tot (LDS, zero on entry; optional) takes the
+// keys of all bins, complete once the pick's closing barrier is passed.
 template <int BLOCK>
-__device__ __forceinline__ void pick_pre(SelState &ss, const uint32_t *pre, uint32_t nb, u64 *scratch, u64 *cnt0) {
+__device__ __forceinline__ void pick_pre(SelState &ss, const uint32_t *pre, uint32_t nb, u64 *scratch, u64 *cnt0,
+                                         u64 *tot = nullptr) {
     constexpr int PER = NBINS / BLOCK;
     u64 h0[PER];
+    u64 mine = 0;
 #pragma unroll
     for (int j = 0; j < PER; ++j) {
         const uint32_t b = threadIdx.x * PER + j;
@@ -79,6 +85,11 @@ __device__ __forceinline__ void pick_pre(SelState &ss, const uint32_t *pre, uint
 #pragma unroll
             for (int c = 0; c < PRE_COPIES; ++c) sum += pre[c * PRE_BINS + b];
         h0[j] = sum;
+        mine += sum;
+    }
+    if (tot) {
+        const u64 w = wave_incl_scan64(mine);
+        if ((threadIdx.x & (WAVE - 1)) == WAVE - 1 && w) atomicAdd(tot, w);
     }
     pick_state<BLOCK, PER>(ss, h0, h0, true, scratch, nullptr, cnt0);
 }
@@ -240,6 +251,7 @@ __global__ __launch_bounds__(DENSE_BLK) void k_head(StepArgs a, CoopArgs x, cons
 //     its call parity, which a graph freezes.)
 constexpr int FIN_LDS_KEYS = 32768;  // LDS-resident keys per workgroup (128 KiB of dynamic LDS)
 constexpr int FIN_UNROLL = 4;        // 16-B loads in flight per thread (1024-thread workgroups: <= 128 VGPRs)
+constexpr uint32_t LAST_FORM_SHIFT = 12;  // k_finish's form in the last-call word, above the host's tag bits
 
 __device__ __forceinline__ void finish_keys(uint32_t (*lh)[NBINS], const HistPlan &plan, const uint4 &x, bool xr,
                                             uint32_t valid4) {
@@ -272,15 +284,107 @@ constexpr uint32_t TAIL_STAGE = 2 * NBINS;  // keys a workgroup stages in LDS (t
 // slice lands ~3.5 us after the decide either way; reading and picking
 // PreHist takes ~4 us more, profiles/r5_select_stamps.txt.)
 
-// (a template only so that each k_finish<F32> has its own copy, inlined into
-// its one caller as before: shared between the two kernels it was compiled as
-// a call and k_finish<false> no longer matched the int32-only build)
+// a key of another bin of the entry digit than the picked one: pads the last
+// 16-byte vector of the finisher's keys and matches no later prefix either
+__device__ __forceinline__ uint32_t finisher_pad(const SelState &ss) {
+    return ss.base + ((ss.t[0].prefix ^ 1u) << (ss.W - ss.t[0].done));
+}
+
+// The finisher's part of both forms (finish_tail, finish_gather): `total` keys
+// of the picked bin lie in res, padded to whole vectors with finisher_pad; one
+// workgroup resolves the remaining digits with block barriers only.
+template <bool F32>
+__device__ __forceinline__ void finish_levels(const StepArgs &a, SelState &ss, const uint4 *res, uint32_t total,
+                                              uint32_t (*lh)[NBINS], u64 *scratch) {
+    __shared__ uint32_t s_ln;
+    __shared__ uint32_t s_list[WAVE];
+    __shared__ u64 s_c;
+    const uint32_t W = ss.W, base = ss.base, nq = (total + 3) / 4, pad = finisher_pad(ss);
+    const int lane = threadIdx.x & (WAVE - 1);
+    // the remaining digits in LDS, one target (pick_state ends with a barrier)
+    constexpr int PER = NBINS / DENSE_BLK;
+    for (int it = 0; ss.mode == MODE_CAND || ss.mode == MODE_FULL; ++it) {  // block-uniform
+        (void)it;
+        const uint32_t dn = ss.t[0].done, pf = ss.t[0].prefix, d = digit_bits(ss, dn);
+        const uint32_t msh = W - dn, sh = W - dn - d, mask = (1u << d) - 1u;
+        for (int i = threadIdx.x; i < NBINS / 4; i += DENSE_BLK) reinterpret_cast<uint4 *>(&lh[0][0])[i] = make_uint4(0, 0, 0, 0);
+        __syncthreads();
+        auto add = [&](uint32_t key) {
+            const uint32_t v = key - base;
+            if ((v >> msh) == pf) atomicAdd(&lh[0][(v >> sh) & mask], 1u);  // msh < 32: dn >= 1
+        };
+        for (uint32_t v = threadIdx.x; v < nq; v += DENSE_BLK) {
+            const uint4 q = res[v];
+            add(q.x);
+            add(q.y);
+            add(q.z);
+            add(q.w);
+        }
+        __syncthreads();
+        u64 h0[PER];
+#pragma unroll
+        for (int j = 0; j < PER; ++j) h0[j] = lh[0][threadIdx.x * PER + j];
+        pick_state<DENSE_BLK, PER>(ss, h0, h0, true, scratch, nullptr, &s_c);
+#ifdef KTH_STAMPS_BUILD
+        if (it < 2) KTH_STAMP(a, 1 + it);  // diagnostic only: the finisher overwrites its own early stamps
+#endif
+        // <= 64 keys left in the picked bin (uniform keys: ~8): list them and
+        // rank them in one wave instead of another histogram level
+        if ((ss.mode == MODE_CAND || ss.mode == MODE_FULL) && s_c <= (u64)WAVE) {  // block-uniform
+            const uint32_t dl = ss.t[0].done, pl = ss.t[0].prefix, msl = W - dl;  // 1 <= dl < W
+            if (threadIdx.x == 0) s_ln = 0;
+            __syncthreads();
+            auto put = [&](uint32_t key) {  // wave-convergent
+                const bool m = ((key - base) >> msl) == pl;
+                const u64 b = __ballot(m);
+                if (b == 0) return;
+                uint32_t at = 0;
+                if (lane == 0) at = atomicAdd(&s_ln, (uint32_t)__popcll(b));
+                at = __shfl(at, 0, WAVE);
+                const uint32_t i = at + (uint32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32),
+                                                                             __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+                if (m && i < (uint32_t)WAVE) s_list[i] = key;
+            };
+            for (uint32_t v0 = 0; v0 < nq; v0 += DENSE_BLK) {
+                const uint32_t v = v0 + threadIdx.x;
+                const uint4 q = v < nq ? res[v] : make_uint4(pad, pad, pad, pad);
+                put(q.x);
+                put(q.y);
+                put(q.z);
+                put(q.w);
+            }
+            __syncthreads();
+            if (threadIdx.x < WAVE) {
+                const uint32_t ln = s_ln < (uint32_t)WAVE ? s_ln : (uint32_t)WAVE;
+                const uint32_t mine = (uint32_t)lane < ln ? s_list[lane] : 0u;
+                uint32_t lt = 0, le = 0;
+                for (uint32_t j = 0; j < ln; ++j) {
+                    const uint32_t o = s_list[j];
+                    lt += o < mine ? 1u : 0u;
+                    le += o <= mine ? 1u : 0u;
+                }
+                const u64 kk = ss.t[0].k;
+                const bool hit = (uint32_t)lane < ln && (u64)lt < kk && kk <= (u64)le;
+                if (hit) ss.answer = mine;  // equal keys write the same value
+                if (__ballot(hit) == 0 && lane == 0) ss.error = 33;
+            }
+            __syncthreads();
+            if (threadIdx.x == 0) ss.mode = MODE_DONE;
+            __syncthreads();
+            break;
+        }
+    }
+    KTH_STAMP(a, 3);
+}
+
+// (returns true on the finisher; *total_out: its keys, loaded into res, unless
+// ss.error.  A template so that each k_finish<F32> has its own copy; k_finish
+// inlines it at its one call, like finish_gather and the advance.)
 template <bool F32>
 __device__ bool finish_tail(const StepArgs &a, SelState &ss, const CoopArgs &x, uint4 *res, u64 nk, bool xr,
-                            uint32_t (*lh)[NBINS], u64 *scratch) {
-    __shared__ uint32_t s_n, s_last, s_total, s_ln;
-    __shared__ uint32_t s_list[WAVE];
-    __shared__ u64 s_off, s_c;
+                            uint32_t (*lh)[NBINS], u64 *scratch, uint32_t *total_out) {
+    __shared__ uint32_t s_n, s_last, s_total;
+    __shared__ u64 s_off;
     const uint32_t X = xr ? 0x80000000u : 0u;
     const uint32_t W = ss.W, base = ss.base, done = ss.t[0].done, prefix = ss.t[0].prefix;
     const uint32_t psh = W - done;  // done >= 1: a level was picked
@@ -421,80 +525,80 @@ __device__ bool finish_tail(const StepArgs &a, SelState &ss, const CoopArgs &x, 
         __syncthreads();
     }
     KTH_STAMP(a, 6);
-    // the remaining digits in LDS, one target (pick_state ends with a barrier)
-    constexpr int PER = NBINS / DENSE_BLK;
-    for (int it = 0; ss.mode == MODE_CAND || ss.mode == MODE_FULL; ++it) {  // block-uniform
-        (void)it;
-        const uint32_t dn = ss.t[0].done, pf = ss.t[0].prefix, d = digit_bits(ss, dn);
-        const uint32_t msh = W - dn, sh = W - dn - d, mask = (1u << d) - 1u;
-        for (int i = threadIdx.x; i < NBINS / 4; i += DENSE_BLK) reinterpret_cast<uint4 *>(&lh[0][0])[i] = make_uint4(0, 0, 0, 0);
-        __syncthreads();
-        auto add = [&](uint32_t key) {
-            const uint32_t v = key - base;
-            if ((v >> msh) == pf) atomicAdd(&lh[0][(v >> sh) & mask], 1u);  // msh < 32: dn >= 1
-        };
-        for (uint32_t v = threadIdx.x; v < nq; v += DENSE_BLK) {
-            const uint4 q = res[v];
-            add(q.x);
-            add(q.y);
-            add(q.z);
-            add(q.w);
+    *total_out = total;
+    return true;
+}
+
+// The grouped form of the finish (workgroup 0 alone): k_main<0> left the
+// candidates grouped by the digit just picked from PreHist and a directory row
+// per workgroup (GDIR_*), so the picked bin's keys are gathered straight into
+// LDS: thread g reads row g's two prefix entries and base, a block scan of the
+// counts gives each source's place, and the keys are copied with every thread
+// taking keys i, i + DENSE_BLK, ... of the bin (its source found by a binary
+// search of the places: a dense source serialises no thread), GATHER_UNROLL
+// loads in flight.  No slice load, scan, reservation, arrival or wait.
+// Returns false (ss.error set) when the directory disagrees with PreHist's
+// count of the bin, which bounds every index below.
+struct FinGroup {
+    const uint8_t *dir;  // k_main<0>'s group directory, or null: the slice tail
+    uint32_t rows;       // its rows (k_main<0>'s workgroups)
+};
+constexpr int GATHER_UNROLL = 8;
+template <bool F32>
+__device__ bool finish_gather(const StepArgs &a, SelState &ss, const FinGroup &fg, uint4 *res, u64 cnt0,
+                              uint32_t (*lh)[NBINS], u64 *scratch, uint32_t *total_out) {
+    static_assert(2 * NBINS * 4 >= DENSE_BLK * 12, "the places and sources fit the histogram's LDS");
+    uint32_t *off = &lh[0][0];                       // [DENSE_BLK] first LDS key of each source
+    u64 *src = reinterpret_cast<u64 *>(&lh[1][0]);   // [DENSE_BLK] its first key of the bin in the candidate buffer
+    const uint32_t b = ss.t[0].prefix, pad = finisher_pad(ss);  // (the first digit: the prefix is the bin)
+    uint32_t cnt = 0;
+    u64 s0 = 0;
+    if (threadIdx.x < fg.rows) {
+        const uint8_t *row = fg.dir + (size_t)threadIdx.x * GDIR_ROW_BYTES;
+        const uint16_t *P = reinterpret_cast<const uint16_t *>(row);
+        const uint32_t p0 = P[b], p1 = P[b + 1];
+        s0 = *reinterpret_cast<const u64 *>(row + GDIR_BASE_OFF) + p0;
+        cnt = p1 >= p0 ? p1 - p0 : 0u;
+    }
+    u64 total;
+    off[threadIdx.x] = (uint32_t)block_exclusive_scan<DENSE_BLK>((u64)cnt, scratch, &total);
+    src[threadIdx.x] = s0;
+    __syncthreads();
+    KTH_STAMP(a, 5);
+    if (total != cnt0 || total > (u64)FIN_LDS_KEYS) {  // cannot happen: PreHist counted the same keys
+        if (threadIdx.x == 0) {
+            ss.error = 34;
+            ss.mode = MODE_DONE;
         }
         __syncthreads();
-        u64 h0[PER];
+        return false;
+    }
+    const uint32_t tot = (uint32_t)total;
+    uint32_t *rw = reinterpret_cast<uint32_t *>(res);
+    for (uint32_t i0 = 0; i0 < tot; i0 += GATHER_UNROLL * DENSE_BLK) {  // block-uniform
+        uint32_t v[GATHER_UNROLL];
 #pragma unroll
-        for (int j = 0; j < PER; ++j) h0[j] = lh[0][threadIdx.x * PER + j];
-        pick_state<DENSE_BLK, PER>(ss, h0, h0, true, scratch, nullptr, &s_c);
-#ifdef KTH_STAMPS_BUILD
-        if (it < 2) KTH_STAMP(a, 1 + it);  // diagnostic only: the finisher overwrites its own early stamps
-#endif
-        // <= 64 keys left in the picked bin (uniform keys: ~8): list them and
-        // rank them in one wave instead of another histogram level
-        if ((ss.mode == MODE_CAND || ss.mode == MODE_FULL) && s_c <= (u64)WAVE) {  // block-uniform
-            const uint32_t dl = ss.t[0].done, pl = ss.t[0].prefix, msl = W - dl;  // 1 <= dl < W
-            if (threadIdx.x == 0) s_ln = 0;
-            __syncthreads();
-            auto put = [&](uint32_t key) {  // wave-convergent
-                const bool m = ((key - base) >> msl) == pl;
-                const u64 b = __ballot(m);
-                if (b == 0) return;
-                uint32_t at = 0;
-                if (lane == 0) at = atomicAdd(&s_ln, (uint32_t)__popcll(b));
-                at = __shfl(at, 0, WAVE);
-                const uint32_t i = at + (uint32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32),
-                                                                             __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
-                if (m && i < (uint32_t)WAVE) s_list[i] = key;
-            };
-            for (uint32_t v0 = 0; v0 < nq; v0 += DENSE_BLK) {
-                const uint32_t v = v0 + threadIdx.x;
-                const uint4 q = v < nq ? res[v] : make_uint4(pad, pad, pad, pad);
-                put(q.x);
-                put(q.y);
-                put(q.z);
-                put(q.w);
+        for (int u = 0; u < GATHER_UNROLL; ++u) {
+            const uint32_t i = i0 + u * DENSE_BLK + threadIdx.x;
+            v[u] = pad;
+            if (i < tot) {
+                uint32_t s = 0;  // the last source whose place is <= i
+#pragma unroll
+                for (uint32_t step = DENSE_BLK / 2; step; step >>= 1) s += off[s + step] <= i ? step : 0u;
+                const u64 at = src[s] + (i - off[s]);
+                if (at < a.cap) v[u] = load_nt(a.cand + at);
             }
-            __syncthreads();
-            if (threadIdx.x < WAVE) {
-                const uint32_t ln = s_ln < (uint32_t)WAVE ? s_ln : (uint32_t)WAVE;
-                const uint32_t mine = (uint32_t)lane < ln ? s_list[lane] : 0u;
-                uint32_t lt = 0, le = 0;
-                for (uint32_t j = 0; j < ln; ++j) {
-                    const uint32_t o = s_list[j];
-                    lt += o < mine ? 1u : 0u;
-                    le += o <= mine ? 1u : 0u;
-                }
-                const u64 kk = ss.t[0].k;
-                const bool hit = (uint32_t)lane < ln && (u64)lt < kk && kk <= (u64)le;
-                if (hit) ss.answer = mine;  // equal keys write the same value
-                if (__ballot(hit) == 0 && lane == 0) ss.error = 33;
-            }
-            __syncthreads();
-            if (threadIdx.x == 0) ss.mode = MODE_DONE;
-            __syncthreads();
-            break;
+        }
+#pragma unroll
+        for (int u = 0; u < GATHER_UNROLL; ++u) {
+            const uint32_t i = i0 + u * DENSE_BLK + threadIdx.x;
+            if (i < tot) rw[i] = v[u];
         }
     }
-    KTH_STAMP(a, 3);
+    if (threadIdx.x < 3 && tot + threadIdx.x < ((tot + 3) & ~3u)) rw[tot + threadIdx.x] = pad;
+    __syncthreads();
+    KTH_STAMP(a, 6);
+    *total_out = tot;
     return true;
 }
 
@@ -503,23 +607,31 @@ __device__ bool finish_tail(const StepArgs &a, SelState &ss, const CoopArgs &x, 
 // loaded, so the LDS slice, the tail and every later digit see the int32 form.
 // last_tag: what the writer leaves in *x.last (kth_api.hip LastCall).
 template <bool F32 = false>
-__global__ __launch_bounds__(DENSE_BLK) void k_finish(StepArgs a, CoopArgs x, uint32_t last_tag) {
+__global__ __launch_bounds__(DENSE_BLK) void k_finish(StepArgs a, CoopArgs x, uint32_t last_tag, FinGroup fg) {
     __shared__ SelState ss;
     __shared__ u64 scratch[2 * (DENSE_BLK / WAVE) + 8];
     __shared__ __attribute__((aligned(16))) uint32_t lh[2][NBINS];
     extern __shared__ uint4 res[];  // FIN_LDS_KEYS / 4 entries (dynamic)
     __shared__ uint32_t s_base[BAR_NG];
-    __shared__ u64 s_cnt0;
+    __shared__ u64 s_cnt0, s_ptot;
     KTH_STAMP(a, 0);
+    if (threadIdx.x == 0) s_ptot = 0;  // (the barriers of the advance lie before its use)
     GridBar gb = grid_bar_init(x.bar, s_base);
     for (int i = threadIdx.x; i < 2 * NBINS / 4; i += DENSE_BLK) reinterpret_cast<uint4 *>(&lh[0][0])[i] = make_uint4(0, 0, 0, 0);
     const uint32_t pre_incomplete = x.pre ? x.pre[PRE_INCOMPLETE] : 1u;  // (loaded beside the state)
-    advance<DENSE_BLK>(ss, a, scratch);
+    // (inlined here, as the two finishers below: called, they read their
+    // arguments back from scratch memory, a round trip each -- the decide took
+    // 11 us instead of 4.4)
+    [[clang::always_inline]] advance<DENSE_BLK>(ss, a, scratch);
     if (threadIdx.x == 0 && (ss.mode == MODE_CAND || ss.mode == MODE_FULL) && ss.t[0].done == 0)
         ss.d0 = fin_first_digit(ss.W);
     __syncthreads();
     // the candidates' first digit from k_main (grid-uniform: every workgroup reads the same words)
     const bool use_pre = pre_incomplete == 0u && ss.mode == MODE_CAND && ss.t[0].done == 0;
+    // ... and its candidates grouped by that digit: PreHist complete means every
+    // row of the directory is this launch's (grid-uniform; the barrier hook keeps
+    // the slice tail, whose wait it fails)
+    const bool group = use_pre && fg.dir != nullptr && fg.rows <= (uint32_t)DENSE_BLK && !x.fault;
     KTH_STAMP(a, 1);
     // the domain (block-uniform): candidates or the input, and this workgroup's slice
     const uint32_t mode0 = ss.mode;
@@ -535,7 +647,7 @@ __global__ __launch_bounds__(DENSE_BLK) void k_finish(StepArgs a, CoopArgs x, ui
         b0 = min((u64)blockIdx.x * per, count);
         nk = min(per, count - b0);
     }
-    bool ok = true, tail = false;
+    bool ok = true, tail = false, gather = false;
     int levels = 0;  // levels run (block-uniform)
     for (int L = 0; L < FIN_LEVELS; ++L) {
         const uint32_t mode = ss.mode;
@@ -549,6 +661,26 @@ __global__ __launch_bounds__(DENSE_BLK) void k_finish(StepArgs a, CoopArgs x, ui
             __syncthreads();
         }
         const bool pre0 = L == 0 && use_pre;  // the digit is picked from PreHist below
+        // first digit: every key lands, so every workgroup flushes nearly every
+        // bin -- into NBINS / bins copies; later digits see one bin's keys
+        const uint32_t nb = plan.mask[0] + 1u, copies = L == 0 ? NBINS / nb : 1u;
+        // Grouped candidates: the pick comes first, and a bin that fits one
+        // workgroup's LDS needs no slice -- workgroup 0 gathers it and the
+        // others leave, having touched nothing.  Every workgroup takes the same
+        // side: all pick from the same PreHist, and a heavier bin sends all of
+        // them on to the slices below.  Workgroup 0 clears PreHist when it is
+        // done, which a workgroup that starts late may see: it then finds fewer
+        // keys than the candidate count (cleared words read 0), which means
+        // the gather was chosen, so it leaves too.
+        if (pre0 && group) {
+            pick_pre<DENSE_BLK>(ss, x.pre, nb, scratch, &s_cnt0, &s_ptot);
+            if (s_ptot != ss.cnt[C_IN] ||
+                ((ss.mode == MODE_CAND || ss.mode == MODE_FULL) && s_cnt0 <= (u64)FIN_LDS_KEYS)) {  // block-uniform
+                gather = true;
+                KTH_STAMP(a, 4);
+                break;
+            }
+        }
         if (resident) {
             const uint32_t nv = (uint32_t)((nk + 3) / 4);
             if (L == 0) {  // HBM -> registers -> histogram + LDS (pre0: LDS only)
@@ -631,11 +763,8 @@ __global__ __launch_bounds__(DENSE_BLK) void k_finish(StepArgs a, CoopArgs x, ui
         }
 #endif
         u64 *slot = x.slots + (size_t)L * STATS_WORDS;
-        // first digit: every key lands, so every workgroup flushes nearly every
-        // bin -- into NBINS / bins copies; later digits see one bin's keys
-        const uint32_t nb = plan.mask[0] + 1u, copies = L == 0 ? NBINS / nb : 1u;
         if (pre0) {
-            pick_pre<DENSE_BLK>(ss, x.pre, nb, scratch, &s_cnt0);
+            if (!group) pick_pre<DENSE_BLK>(ss, x.pre, nb, scratch, &s_cnt0);  // (group: picked above)
         } else {
             if (copies > 1)
                 hist_flush_copies<DENSE_BLK>(lh, nb, copies, slot);
@@ -657,13 +786,30 @@ __global__ __launch_bounds__(DENSE_BLK) void k_finish(StepArgs a, CoopArgs x, ui
             break;
         }
     }
-    // no tail: every workgroup has picked the last level before its slot and PreHist are cleared below
-    if (levels > 0 && !tail) grid_sync(gb, s_base, ok);
-    grid_bar_finish(gb, s_base);
-    bool writer = blockIdx.x == 0;
-    if (tail) {
-        writer = finish_tail<F32>(a, ss, x, res, nk, xr, lh, scratch);
+    const u64 spread = (u64)blockIdx.x * DENSE_BLK + threadIdx.x, step = (u64)gridDim.x * DENSE_BLK;
+    if (gather) {
+        // no slot, tail word or barrier counter was touched, so nothing has to be
+        // left consistent; the sample phase's slots, which no pick of this launch
+        // reads, are cleared by all before the others leave
+        for (u64 i = spread; i < x.zero2_words; i += step) x.zero2[i] = 0;
+        if (blockIdx.x != 0) {
+            KTH_STAMP(a, 7);
+            return;
+        }
     }
+    // no tail: every workgroup has picked the last level before its slot and PreHist are cleared below
+    if (levels > 0 && !tail && !gather) grid_sync(gb, s_base, ok);
+    grid_bar_finish(gb, s_base);  // (gather: no barrier was passed, the bases stay)
+    bool writer = blockIdx.x == 0, finisher = false;
+    uint32_t fin_keys = 0;  // the finisher's keys in res
+    if (tail) {
+        [[clang::always_inline]] writer = finisher = finish_tail<F32>(a, ss, x, res, nk, xr, lh, scratch, &fin_keys);
+    } else if (gather && (ss.mode == MODE_CAND || ss.mode == MODE_FULL)) {
+        [[clang::always_inline]] finisher = finish_gather<F32>(a, ss, fg, res, s_cnt0, lh, scratch, &fin_keys);
+    }
+    if (finisher && !ss.error) finish_levels<F32>(a, ss, res, fin_keys, lh, scratch);  // block-uniform
+    // how the launch ended (KTH_FINISH_*, kth_ctx_last_finish_form), beside the tag
+    const uint32_t form = levels == 0 ? 1u : tail ? 2u : gather ? 3u : 4u;
     if (writer && threadIdx.x == 0) {
         SelState o = ss;
         const uint32_t berr = __hip_atomic_exchange(x.bar + BAR_ERR, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -678,7 +824,13 @@ __global__ __launch_bounds__(DENSE_BLK) void k_finish(StepArgs a, CoopArgs x, ui
             x.d_status[0] = i32_of_key(o.answer);
             x.d_status[1] = (int32_t)o.error;
         }
-        if (x.last) *x.last = last_tag;
+        if (x.last) *x.last = last_tag | form << LAST_FORM_SHIFT;
+    }
+    if (gather) {  // workgroup 0 alone: no slot was added into; PreHist is its to clear
+        for (uint32_t i = threadIdx.x; i < (uint32_t)PRE_WORDS / 4; i += DENSE_BLK)
+            reinterpret_cast<uint4 *>(x.pre)[i] = make_uint4(0, 0, 0, 0);
+        KTH_STAMP(a, 7);
+        return;
     }
     // What this launch used is zero again when it ends (see the head of this
     // section).  With a tail, only the finisher -- the last to arrive, so the
@@ -688,7 +840,6 @@ __global__ __launch_bounds__(DENSE_BLK) void k_finish(StepArgs a, CoopArgs x, ui
     // workgroup is past the barrier above, or no level ran: then no slot was
     // added into, and PreHist (k_main<0> fills it whatever this launch
     // decides) is read by no pick.
-    const u64 spread = (u64)blockIdx.x * DENSE_BLK + threadIdx.x, step = (u64)gridDim.x * DENSE_BLK;
     const u64 shared_words = (u64)(tail ? levels - 1 : levels) * STATS_WORDS;
     for (u64 i = spread; i < shared_words; i += step) x.slots[i] = 0;
     for (u64 i = spread; i < x.zero2_words; i += step) x.zero2[i] = 0;

@@ -113,6 +113,20 @@ constexpr int PRE_COPIES = KTH_PRE_COPIES, PRE_BINS = 1024;  // a first digit of
 static_assert(FIN_D0 <= 10, "PreHist holds a first digit of at most 10 bits");
 constexpr int PRE_WORDS = PRE_COPIES * PRE_BINS + 64;  // u32: the copies, then `incomplete` (own 256-B line)
 constexpr int PRE_INCOMPLETE = PRE_COPIES * PRE_BINS;
+// The group directory: a k_main<0> workgroup whose PreHist share is complete
+// also writes its candidates GROUPED by that digit (bin 0's keys first) and
+// leaves one row here: the exclusive prefix of its PRE_BINS bin counts (u16:
+// a workgroup stages at most 4 * WREG keys; entry PRE_BINS = its candidate
+// count) and the start of its block in the candidate buffer.  k_finish then
+// finds bin b's keys of workgroup g at cand[base_g + P_g[b] .. base_g +
+// P_g[b + 1]) without scanning the candidates (finish_gather).  A row is
+// written on every launch that PreHist is complete for, so none is ever stale
+// when k_finish reads it, and nothing is cleared.
+constexpr int GDIR_BASE_OFF = (PRE_BINS + 4) * 2;  // bytes: the u64 base follows the (padded) u16 prefixes
+constexpr int GDIR_ROW_BYTES = 2304;               // a row, in whole 256-byte lines
+static_assert(GDIR_BASE_OFF % 8 == 0 && GDIR_BASE_OFF + 8 <= GDIR_ROW_BYTES && GDIR_ROW_BYTES % 256 == 0, "row layout");
+static_assert((BLK / WAVE) * WREG <= 65535, "a workgroup's candidate count fits a u16 prefix");
+static_assert(PRE_BINS == 4 * BLK, "k_main<0> scans four bins a thread into one 8-byte row word");
 // the candidate domain of k_finish's decide(): v = key - (lo + 1) in [0, 2^W)
 __device__ __forceinline__ uint32_t cand_width(uint32_t lo, uint32_t hi) {
     const uint32_t range = hi - lo - 2u;
@@ -1096,6 +1110,8 @@ __device__ __forceinline__ void scan_keys(const uint32_t (&xw)[K], uint32_t vali
     }
 }
 
+// TF 0 takes no flags: there `tflags` is the group directory (GDIR_*, one row a
+// workgroup) or null (candidates leave in staging order).
 // TF (top-k variant, kth_topk.hpp): 0 = plain select; 1 / 2 = also record, per
 // full tile, wave and row (the tile's u-th run of 4 * BLK keys), one bit "some
 // key <= hi" (1, k smallest) or "some key >= lo" (2, k largest): bit u of
@@ -1483,11 +1499,7 @@ __global__ __launch_bounds__(BLK) void k_main(StepArgs a, uint32_t *__restrict__
         }
     }
     __syncthreads();
-    if (st.wfill) {  // this wave's final region, at its share of the reservation
-        u64 g = red[5][0];
-        for (int w = 0; w < wid; ++w) g += red[4][w];
-        st.put(g, st.wfill);
-    }
+    bool grouped = false;  // block-uniform (TF 0): the candidates left grouped by their first digit
     if constexpr (TF == 0) {
         if (a.pre_hist) {  // kernel-uniform: the candidates' first digit for k_finish (PreHist)
             __shared__ uint32_t phist[PRE_BINS];
@@ -1523,8 +1535,64 @@ __global__ __launch_bounds__(BLK) void k_main(StepArgs a, uint32_t *__restrict__
                     const uint32_t c = phist[b];
                     if (c) atomicAdd(&dst[b], c);
                 }
+                KTH_STAMP(a, 4);
+                // Grouped copy-out (tflags: the group directory, or null).  The
+                // workgroup's candidates, all still in `region`, leave ordered
+                // by bin, and its row of the directory says where each bin
+                // starts.  Not after a candidate overflow (block-uniform: the
+                // select then takes the fallback over the input).
+                u64 tot = 0;
+#pragma unroll
+                for (int q = 0; q < BLK / WAVE; ++q) tot += red[4][q];
+                const u64 g0 = red[5][0];
+                if (tflags != nullptr && g0 + tot <= a.cap) {
+                    grouped = true;
+                    constexpr int PT = (BLK / WAVE) * WREG / BLK, PQ = WREG / BLK;  // keys a thread, and of one region
+                    static_assert(WREG % BLK == 0 && PT <= 32, "a thread's keys of the flat regions, one validity bit each");
+                    uint32_t *flat = &region[0][0];
+                    // the flat regions' keys into registers (key j of a thread lies in region j / PQ)
+                    uint32_t kk[PT], vm = 0;
+#pragma unroll
+                    for (int j = 0; j < PT; ++j) {
+                        kk[j] = flat[j * BLK + threadIdx.x];
+                        vm |= (uint32_t)((j % PQ) * BLK + threadIdx.x) < (uint32_t)red[4][j / PQ] ? 1u << j : 0u;
+                    }
+                    // bin counts -> exclusive prefix, in place (the scan's barrier is
+                    // behind every thread's reads of phist above) and into the row
+                    const uint32_t c0 = phist[4 * threadIdx.x], c1 = phist[4 * threadIdx.x + 1],
+                                   c2 = phist[4 * threadIdx.x + 2], c3 = phist[4 * threadIdx.x + 3];
+                    const uint32_t inc = wave_incl_scan32(c0 + c1 + c2 + c3);
+                    if (lane == WAVE - 1) scratch[wid] = inc;
+                    __syncthreads();
+                    uint32_t e0 = inc - (c0 + c1 + c2 + c3);
+                    for (int w = 0; w < wid; ++w) e0 += (uint32_t)scratch[w];
+                    const uint32_t e1 = e0 + c0, e2 = e1 + c1, e3 = e2 + c2;
+                    phist[4 * threadIdx.x] = e0;
+                    phist[4 * threadIdx.x + 1] = e1;
+                    phist[4 * threadIdx.x + 2] = e2;
+                    phist[4 * threadIdx.x + 3] = e3;
+                    u64 *row = reinterpret_cast<u64 *>(reinterpret_cast<uint8_t *>(tflags) + (size_t)blockIdx.x * GDIR_ROW_BYTES);
+                    __hip_atomic_store(row + threadIdx.x, (u64)e0 | (u64)e1 << 16 | (u64)e2 << 32 | (u64)e3 << 48,
+                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (threadIdx.x == 0) {
+                        __hip_atomic_store(row + PRE_BINS / 4, tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        __hip_atomic_store(row + GDIR_BASE_OFF / 8, g0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    }
+                    __syncthreads();
+                    // each key to its bin's next place (phist[b] ends as bin b's end)
+#pragma unroll
+                    for (int j = 0; j < PT; ++j)
+                        if ((vm >> j) & 1u) flat[atomicAdd(&phist[(kk[j] - base) >> sh], 1u)] = kk[j];
+                    __syncthreads();
+                    for (uint32_t i = threadIdx.x; i < (uint32_t)tot; i += BLK) put_cand(&cand_out[g0 + i], flat[i]);
+                }
             }
         }
+    }
+    if (!grouped && st.wfill) {  // this wave's final region, at its share of the reservation
+        u64 g = red[5][0];
+        for (int w = 0; w < wid; ++w) g += red[4][w];
+        st.put(g, st.wfill);
     }
     KTH_STAMP(a, 5);
 }

@@ -35,8 +35,14 @@ from ._lib import (  # noqa: F401
     KTH_EINTERNAL,
     KTH_EINVAL,
     KTH_ENODEV,
+    KTH_FINISH_COUNTS,
+    KTH_FINISH_GROUPED,
+    KTH_FINISH_LEVELS,
+    KTH_FINISH_NONE,
+    KTH_FINISH_SLICES,
     KTH_HOOK_FAULT_BARRIER,
     KTH_HOOK_FAULT_TOPK_RANK,
+    KTH_HOOK_FINISH_SLICES,
     KTH_HOOK_K16_MISS,
     KTH_HOOK_TOPK_SEG_CAP,
     KTH_MULTI_MAX_RANKS,
@@ -351,6 +357,13 @@ class Selector:
         st = KthStats()
         check(LIB.kth_ctx_last_stats(self._ctx, ctypes.byref(st)), "kth_ctx_last_stats")
         return st.as_dict()
+
+    def finish_form(self):
+        """How the cooperative finish of the last select ended: one of KTH_FINISH_*
+        (kth_ctx_last_finish_form; synchronises)."""
+        form = ctypes.c_int(-1)
+        check(LIB.kth_ctx_last_finish_form(self._ctx, ctypes.byref(form)), "kth_ctx_last_finish_form")
+        return form.value
 
     def rows(self, d_keys, rows, cols, k, d_out, f32=False):
         fn = LIB.kth_select_rows_f32 if f32 else LIB.kth_select_rows_i32

@@ -31,6 +31,9 @@ KTH_MULTI_MAX_RANKS = 8
 # kth_ctx_test_hook (tests only): fault injectors, off in every new ctx
 KTH_HOOK_FAULT_TOPK_RANK, KTH_HOOK_FAULT_BARRIER, KTH_HOOK_TOPK_SEG_CAP = 1, 2, 3
 KTH_HOOK_K16_MISS = 4
+KTH_HOOK_FINISH_SLICES = 5
+# kth_ctx_last_finish_form: how the cooperative finish of the last select ended
+KTH_FINISH_NONE, KTH_FINISH_COUNTS, KTH_FINISH_SLICES, KTH_FINISH_GROUPED, KTH_FINISH_LEVELS = range(5)
 
 c_i32p = ctypes.POINTER(ctypes.c_int32)
 c_u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -117,6 +120,7 @@ PROTOS = {
     "kth_ctx_last_stats": (ctypes.c_int, [c_vp, ctypes.POINTER(KthStats)]),
     "kth_ctx_coop": (ctypes.c_int, [c_vp]),
     "kth_ctx_test_hook": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int64]),
+    "kth_ctx_last_finish_form": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_int)]),
     "kth_ctx_enable_timing": (ctypes.c_int, [c_vp, ctypes.c_int]),
     "kth_ctx_take_timing": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double),
                                            ctypes.POINTER(ctypes.c_double)]),
