@@ -350,6 +350,37 @@ int kth_topk_rows_i32(kth_ctx *ctx, const int32_t *d_keys, int64_t rows, int32_t
 int kth_topk_rows_f32(kth_ctx *ctx, const float *d_keys, int64_t rows, int32_t cols, int32_t k, int largest,
                       float *d_vals, int32_t *d_idx);
 
+/* --- 16-bit rows: k-th and top-k per row of 2-byte keys ----------------------
+ * kth_select_rows_* and kth_topk_rows_* for int16, uint16, float16 and
+ * bfloat16 rows, read as they are (2 bytes a key; no widened copy).  d_keys is
+ * a row-major rows x cols matrix of 2-byte words in device memory; kind is
+ * KTH_K16_I16 / U16 / F16 / BF16 and the order is kth_k16_order_key's: -0.0 <
+ * +0.0, subnormals distinct, every NaN (either sign, any payload) equal to
+ * every other and above +inf.  1 <= k <= cols <= KTH_ROWS16_MAX_COLS for both.
+ *   select: d_out[r] = the bits of the k-th smallest element of row r; a NaN
+ *     comes back canonical (0x7E00 / 0x7FC0).
+ *   top-k: the k smallest keys of each row (largest != 0: the k largest) with
+ *     their columns, in column order; of the keys equal to the k-th, the first
+ *     ones by column.  d_vals: rows x k 2-byte values (NaN canonical), d_idx:
+ *     rows x k int32 columns; either may be NULL, not both.  NaNs come last
+ *     for smallest and first for largest, as in kth_topk_rows_f32.
+ * KTH_EINVAL before any device work: a NULL ctx or keys, no output pointer,
+ * rows < 0, a bad cols, k or kind.  rows == 0 returns KTH_OK and launches
+ * nothing.  Asynchronous on the ctx stream; no ctx scratch, no allocation and
+ * no host synchronisation.  As the other rows calls, not claimed capturable.
+ * d_keys, d_out and d_vals need only 2-byte alignment and any cols is exact;
+ * the fast path is a 16-byte aligned d_keys with cols % 8 == 0 (every row
+ * then starts on a 16-byte boundary and is read with 16-byte loads), anything
+ * else is read with guarded 2-byte loads.
+ * One wavefront per row, the row held in registers as packed pairs; an order
+ * key of 16 bits is two 8-bit digits, so every row takes the same two
+ * histogram passes whatever its values (csrc/kth_rows16.hpp). */
+#define KTH_ROWS16_MAX_COLS 8192
+int kth_select_rows_k16(kth_ctx *ctx, const void *d_keys, int64_t rows, int32_t cols, int32_t k,
+                        int kind, uint16_t *d_out);
+int kth_topk_rows_k16(kth_ctx *ctx, const void *d_keys, int64_t rows, int32_t cols, int32_t k, int largest,
+                      int kind, uint16_t *d_vals, int32_t *d_idx);
+
 /* --- top-k of one array ------------------------------------
  * The k smallest keys of d_keys[0..n) (largest != 0: the k largest) with their
  * int64 indices, in index order; of the keys equal to the k-th, the first ones

@@ -821,6 +821,57 @@ int rows_entry(kth_ctx *c, const void *d_keys, int64_t rows, int32_t cols, int32
                                   static_cast<uint32_t *>(d_vals), d_idx);
 }
 
+// 16-bit rows (kth_rows16.hpp): KW packed words per lane by cols, the 16-byte
+// load path for an aligned base with cols % 8 == 0, else the guarded one.
+static_assert(KTH_ROWS16_MAX_COLS == kth::R16_MAX_COLS, "include/kth.h 16-bit row limit");
+template <bool FLT, int KW, bool TOPK>
+void launch_rows16_kw(kth_ctx *c, bool vec, int g, const uint16_t *d_keys, u64 R, uint32_t C, uint32_t K, int kind,
+                      uint32_t flip, uint16_t *d_out, uint16_t *vals, int32_t *idx) {
+    if (vec)
+        kth::k_rows16<FLT, KW, true, TOPK><<<g, kth::RW_BLOCK, 0, c->stream>>>(d_keys, R, C, K, kind, flip, d_out, vals, idx);
+    else
+        kth::k_rows16<FLT, KW, false, TOPK><<<g, kth::RW_BLOCK, 0, c->stream>>>(d_keys, R, C, K, kind, flip, d_out, vals, idx);
+}
+
+template <bool FLT, bool TOPK>
+int launch_rows16(kth_ctx *c, const uint16_t *d_keys, int64_t rows, int32_t cols, int32_t k, int kind, uint32_t flip,
+                  uint16_t *d_out, uint16_t *vals, int32_t *idx) {
+    const bool vec = (reinterpret_cast<uintptr_t>(d_keys) & 15u) == 0 && cols % 8 == 0;
+    const int rows_per_wg = kth::RW_BLOCK / kth::WAVE;
+    const int64_t g64 = (rows + rows_per_wg - 1) / rows_per_wg;  // one row per wave
+    if (g64 > 0x7FFFFFFF) return KTH_EINVAL;
+    const int g = (int)g64;
+    const u64 R = (u64)rows;
+    const uint32_t C = (uint32_t)cols, K = (uint32_t)k;
+    if (cols <= 512)
+        launch_rows16_kw<FLT, 4, TOPK>(c, vec, g, d_keys, R, C, K, kind, flip, d_out, vals, idx);
+    else if (cols <= 1024)
+        launch_rows16_kw<FLT, 8, TOPK>(c, vec, g, d_keys, R, C, K, kind, flip, d_out, vals, idx);
+    else if (cols <= 2048)
+        launch_rows16_kw<FLT, 16, TOPK>(c, vec, g, d_keys, R, C, K, kind, flip, d_out, vals, idx);
+    else if (cols <= 4096)
+        launch_rows16_kw<FLT, 32, TOPK>(c, vec, g, d_keys, R, C, K, kind, flip, d_out, vals, idx);
+    else
+        launch_rows16_kw<FLT, 64, TOPK>(c, vec, g, d_keys, R, C, K, kind, flip, d_out, vals, idx);
+    return launch_check();
+}
+
+// The two 16-bit rows entry points: the argument check and the launch.
+template <bool TOPK>
+int rows16_entry(kth_ctx *c, const void *d_keys, int64_t rows, int32_t cols, int32_t k, int kind, uint16_t *d_out,
+                 int largest = 0, uint16_t *d_vals = nullptr, int32_t *d_idx = nullptr) {
+    const bool has_out = TOPK ? d_vals || d_idx : d_out != nullptr;
+    if (!c || !d_keys || !has_out || rows < 0 || cols < 1 || cols > KTH_ROWS16_MAX_COLS || k < 1 || k > cols ||
+        kind < KTH_K16_I16 || kind > KTH_K16_BF16)
+        return KTH_EINVAL;
+    if (rows == 0) return KTH_OK;
+    KTH_TRY(set_device(c));
+    const uint16_t *keys = static_cast<const uint16_t *>(d_keys);
+    const uint32_t flip = TOPK && largest ? 0xFFFFFFFFu : 0u;
+    return kth::k16_float(kind) ? launch_rows16<true, TOPK>(c, keys, rows, cols, k, kind, flip, d_out, d_vals, d_idx)
+                                : launch_rows16<false, TOPK>(c, keys, rows, cols, k, kind, flip, d_out, d_vals, d_idx);
+}
+
 // ------------------------------------------------------- ctx creation, in parts
 // Every tuning variable of a ctx (design exploration and A/B runs; unset: the
 // defaults in kth_ctx).  Needs c->num_cu.  Read elsewhere: KTH_STAMPS (the
@@ -1825,6 +1876,16 @@ int kth_topk_rows_i32(kth_ctx *c, const int32_t *d_keys, int64_t rows, int32_t c
 int kth_topk_rows_f32(kth_ctx *c, const float *d_keys, int64_t rows, int32_t cols, int32_t k, int largest,
                       float *d_vals, int32_t *d_idx) {
     return rows_entry<true, true>(c, d_keys, rows, cols, k, nullptr, largest, d_vals, d_idx);
+}
+
+int kth_select_rows_k16(kth_ctx *c, const void *d_keys, int64_t rows, int32_t cols, int32_t k, int kind,
+                        uint16_t *d_out) {
+    return rows16_entry<false>(c, d_keys, rows, cols, k, kind, d_out);
+}
+
+int kth_topk_rows_k16(kth_ctx *c, const void *d_keys, int64_t rows, int32_t cols, int32_t k, int largest, int kind,
+                      uint16_t *d_vals, int32_t *d_idx) {
+    return rows16_entry<true>(c, d_keys, rows, cols, k, kind, nullptr, largest, d_vals, d_idx);
 }
 
 }  // extern "C"

@@ -57,6 +57,7 @@ from ._lib import (  # noqa: F401
     KTH_PATH_RADIX,
     KTH_PATH_WINDOW,
     KTH_PATH_WINDOW_FALLBACK,
+    KTH_ROWS16_MAX_COLS,
     KTH_ROWS_MAX_COLS,
     KTH_STATS_WORDS,
     KTH_TOPK_MAX_COLS,
@@ -162,6 +163,17 @@ def _k16_kind(x, kind, what="keys"):
             raise ValueError(f"unknown 16-bit key kind {kind!r}")
         return K16_KINDS[kind]
     return int(kind)
+
+
+def _k16_same_kind(keys, out, kind, what):
+    """An output of the 16-bit rows calls: a 2-byte dtype that names the call's
+    kind, or the keys' own dtype (int16 words carrying bfloat16 bits, kind="bf16",
+    come back as int16 words).  Anything else is a TypeError."""
+    dt = getattr(out, "dtype", None)
+    if dt is None:
+        return
+    if _k16_kind(out, None, what) != kind and str(dt) != str(getattr(keys, "dtype", None)):
+        raise TypeError(f"{what} must have the keys' 16-bit kind, got {dt}")
 
 
 def _k16_host_keys(keys):
@@ -376,6 +388,31 @@ class Selector:
         check(fn(self._ctx, _ptr(d_keys), int(rows), int(cols), int(k), 1 if largest else 0,
                  _ptr(d_vals) if d_vals is not None else None, _ptr(d_idx) if d_idx is not None else None),
               "kth_topk_rows")
+
+    def rows16(self, d_keys, rows, cols, k, d_out, kind=None):
+        """Per row of a rows x cols matrix of 16-bit device keys: the bits of the
+        k-th smallest into the 2-byte element d_out[r] (kth_select_rows_k16;
+        asynchronous on the ctx stream).  `kind` as _k16_kind; d_out must be a
+        2-byte dtype of the keys' kind.  Nothing is converted."""
+        kind = _k16_kind(d_keys, kind, "d_keys")
+        _k16_same_kind(d_keys, d_out, kind, "d_out")
+        check(LIB.kth_select_rows_k16(self._ctx, _ptr(d_keys), int(rows), int(cols), int(k), kind, _ptr(d_out)),
+              "kth_select_rows_k16")
+
+    def topk_rows16(self, d_keys, rows, cols, k, d_vals=None, d_idx=None, largest=False, kind=None):
+        """Per row of 16-bit device keys: the k smallest (largest=True: largest)
+        keys and their int32 columns, in column order, ties broken by column
+        (kth_topk_rows_k16).  d_vals: rows x k 2-byte elements of the keys' kind
+        (a NaN canonical), d_idx: rows x k int32; either may be None, not both."""
+        kind = _k16_kind(d_keys, kind, "d_keys")
+        if d_vals is not None:
+            _k16_same_kind(d_keys, d_vals, kind, "d_vals")
+        dt = getattr(d_idx, "dtype", None)
+        if dt is not None and str(dt).rsplit(".", 1)[-1] != "int32":
+            raise TypeError(f"d_idx must be int32, got {dt}")
+        check(LIB.kth_topk_rows_k16(self._ctx, _ptr(d_keys), int(rows), int(cols), int(k), 1 if largest else 0, kind,
+                                    _ptr(d_vals) if d_vals is not None else None,
+                                    _ptr(d_idx) if d_idx is not None else None), "kth_topk_rows_k16")
 
     def topk(self, d_keys, n, k, d_vals=None, d_idx=None, largest=False, f32=False):
         """The k smallest (largest=True: largest) int32 keys of n device keys and

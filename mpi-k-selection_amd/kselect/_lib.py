@@ -27,6 +27,7 @@ KTH_DIST_DONE = 3  # kth_dist_level: no collective left, call kth_dist_result
 KTH_DIST_MAX_LEVELS = 3
 KTH_ROWS_MAX_COLS = 16384
 KTH_TOPK_MAX_COLS = 4096
+KTH_ROWS16_MAX_COLS = 8192
 KTH_MULTI_MAX_RANKS = 8
 # kth_ctx_test_hook (tests only): fault injectors, off in every new ctx
 KTH_HOOK_FAULT_TOPK_RANK, KTH_HOOK_FAULT_BARRIER, KTH_HOOK_TOPK_SEG_CAP = 1, 2, 3
@@ -130,6 +131,10 @@ PROTOS = {
                                          c_vp, c_vp]),
     "kth_topk_rows_f32": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int,
                                          c_vp, c_vp]),
+    "kth_select_rows_k16": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int,
+                                           c_vp]),
+    "kth_topk_rows_k16": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int,
+                                         ctypes.c_int, c_vp, c_vp]),
     "kth_topk_i32": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, c_vp, c_vp]),
     "kth_topk_f32": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, c_vp, c_vp]),
     "kth_fill_synthetic": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,

@@ -13,6 +13,11 @@ differ between the two logs, a float32 kernel uses more scratch than its
 int32 twin (k_finish keeps 296 bytes a lane in both builds and both kinds), or
 a float32 twin of a grid-barrier kernel (k_head, k_finish: their grids must be
 co-resident) has a lower occupancy than its int32 twin.
+
+    python tools/kernel_resources.py --list k_rows16 this.log > profiles/rows16_kernel_resources.txt
+
+lists every kernel of one log whose name starts with the prefix, one line each;
+exit status 1 when one of them uses scratch.
 """
 import re
 import subprocess
@@ -84,7 +89,22 @@ def fmt(v):
     return " ".join(f"{k} {v.get(k, '?'):>5s}" for _, k in FIELDS) if v else "(not built)"
 
 
+def list_kernels(prefix, path):
+    """One line per kernel of `path` whose name starts with `prefix`; status 1 when one uses scratch."""
+    raw = parse(path)
+    dem = demangle(list(raw))
+    bad = 0
+    for mangled in sorted(raw, key=lambda m: dem[m]):
+        m = re.match(r"(?:void )?kth::(\w+(?:<.*?>)?)\(", dem[mangled])
+        if m and m.group(1).startswith(prefix):
+            print(f"{m.group(1):40s} {fmt(raw[mangled])}")
+            bad |= raw[mangled].get("scratch", "0") != "0"
+    return bad
+
+
 def main():
+    if sys.argv[1] == "--list":  # kernel_resources.py --list k_rows16 this.log
+        return list_kernels(sys.argv[2], sys.argv[3])
     parent, this = table(sys.argv[1]), table(sys.argv[2])
     bad = 0
     for key in sorted({k for k, _ in this} | {k for k, _ in parent}):
