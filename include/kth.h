@@ -294,8 +294,9 @@ int kth_ctx_coop(const kth_ctx *ctx);
 /* --- test hooks (TEST ONLY: never set by the product path) ------------------
  * Fault injectors for the parity tests' error paths.  They are off in every
  * new ctx and are not read from the environment; only this call turns them on.
- *   KTH_HOOK_FAULT_TOPK_RANK  value != 0: kth_topk_i32 selects a neighbouring
- *                             rank, so its count pass must report the bracket
+ *   KTH_HOOK_FAULT_TOPK_RANK  value != 0: kth_topk_i32, kth_topk_f32 and
+ *                             kth_topk_k16 select a neighbouring rank, so
+ *                             their count pass must report the bracket
  *                             failure (outputs unwritten, stats .error set)
  *   KTH_HOOK_FAULT_BARRIER    1: every grid barrier of the cooperative kernels
  *                             reports a timeout; 2: only the next cooperative
@@ -308,12 +309,16 @@ int kth_ctx_coop(const kth_ctx *ctx);
  *   KTH_HOOK_FINISH_SLICES    value != 0: k_finish ignores the group directory
  *                             and takes the slice tail (the grouped form's
  *                             reference); frozen in a captured graph
+ *   KTH_HOOK_K16_TOPK_NOSKIP  value != 0: kth_topk_k16's count pass ignores the
+ *                             flags its streaming pass recorded and loads
+ *                             every tile (the skipping path's reference)
  * Returns KTH_EINVAL for an unknown hook or a bad value. */
 #define KTH_HOOK_FAULT_TOPK_RANK 1
 #define KTH_HOOK_FAULT_BARRIER 2
 #define KTH_HOOK_TOPK_SEG_CAP 3
 #define KTH_HOOK_K16_MISS 4
 #define KTH_HOOK_FINISH_SLICES 5
+#define KTH_HOOK_K16_TOPK_NOSKIP 6 /* (kth_topk_k16) */
 int kth_ctx_test_hook(kth_ctx *ctx, int hook, int64_t value);
 
 /* --- timing (bench) ----------------------------------------------------------
@@ -401,6 +406,49 @@ int kth_topk_i32(kth_ctx *ctx, const int32_t *d_keys, int64_t n, int64_t k, int 
  * pass) is int32 only: float32 keys take the row-word path for that k range. */
 int kth_topk_f32(kth_ctx *ctx, const float *d_keys, int64_t n, int64_t k, int largest, float *d_vals,
                  int64_t *d_idx);
+
+/* --- top-k of one array, 16-bit keys -------------------------------------------
+ * kth_topk_f32's contract for int16, uint16, float16 and bfloat16 keys, read
+ * as 2-byte words (no widened copy): the k smallest keys of d_keys[0..n), or
+ * the k largest when largest != 0, with their int64 indices, in index order;
+ * of the keys equal to the k-th, the first ones by index.  A 16-bit key has
+ * 65536 values, so the k-th value nearly always has a large tie group: the
+ * tie quota is the normal case here.  kind is KTH_K16_I16 / U16 / F16 / BF16
+ * and the order is kth_k16_order_key's: -0.0 < +0.0, subnormals distinct,
+ * every NaN equal to every other and above +inf, so NaNs come last for
+ * smallest and first for largest.
+ * d_vals: k 2-byte words, each the bit pattern of the input element except
+ * that a NaN is written canonical (0x7E00 / 0x7FC0); d_idx: k int64; either
+ * may be NULL, not both.  1 <= k <= n.  KTH_EINVAL before any device work,
+ * outputs untouched: a NULL ctx or keys, no output pointer, a bad n, k or
+ * kind; KTH_ENODEV without a GPU.
+ * d_keys and d_vals need only 2-byte alignment and any n is exact; the fast
+ * path is a 16-byte aligned d_keys, anything else reads the first and last
+ * tile with guarded 2-byte loads (and the select its head and tail).
+ * Asynchronous on the ctx stream, device memory only, no host
+ * synchronisation, no allocation once a call of the same n has run; like the
+ * other top-k calls not claimed graph-capturable.  The call leaves the ctx's
+ * 16-bit scratch (sample histogram, bins, states) and the top-k arrival
+ * counter as it found them, so any eager call or graph replay on the same
+ * ctx may follow (the rule of the graph-capture section above).
+ * It is the 16-bit select (kth_select_k16_async's launches, one rank) plus a
+ * count pass, kth_topk_i32's tile scan and an ordered compaction that reads
+ * only the tiles holding output.  For k <= n / 16384 the select's streaming
+ * pass also records which of its 2048-key rows can hold output, and the
+ * count pass loads only those (decided on the device; a window that missed on
+ * the far side turns the skipping off for that call).
+ * Errors: a device-side inconsistency (counts that do not bracket k: 32)
+ * leaves the outputs unwritten and shows in kth_ctx_last_stats().error.
+ * Stats: kth_ctx_last_stats reports the embedded select (path KTH_PATH_K16 /
+ * KTH_PATH_K16_FALLBACK, answer = the k-th key's bits). */
+int kth_topk_k16(kth_ctx *ctx, const void *d_keys, int64_t n, int64_t k, int largest, int kind,
+                 uint16_t *d_vals, int64_t *d_idx);
+/* Diagnostics of the last kth_topk_k16 on this ctx (synchronises the ctx
+ * stream): *tiles = its count-pass tiles (2048 keys each), *tiles_read = how
+ * many of them the count pass loaded from the input; the rest were proven
+ * empty by the select's streaming pass.  KTH_EINVAL before the first such
+ * call. */
+int kth_ctx_last_topk_k16_tiles(kth_ctx *ctx, uint64_t *tiles, uint64_t *tiles_read);
 
 /* --- synthetic inputs (bench / tests) --------------------------------------
  * Fills d_out[0..n) with the keys of global indices offset..offset+n of an

@@ -21,6 +21,7 @@
 #include "kth_kernels.hip"
 #include "kth_topk.hpp"
 #include "kth_k16.hpp"
+#include "kth_topk16.hpp"
 
 using kth::SelState;
 using kth::StepArgs;
@@ -199,6 +200,11 @@ struct kth_ctx {
     bool k16_ready = false;   // grids sized, k16_hist's LDS granted
     bool k16_dirty = false;   // a k16 call was cut short or failed: re-zero its scratch
     bool k16_miss = false;    // KTH_HOOK_K16_MISS (tests): the sample phase publishes an empty window
+    // kth_topk_k16: k16_main_tf<0 / 1 / 2>'s workgroups; the last call's count-pass tiles (0: none yet)
+    int k16_tf_grid[3] = {};
+    u64 tk16_tiles = 0;
+    DevBuf<u64> tk16_nread;        // ... and the tiles its count pass loaded from the input
+    bool k16_topk_noskip = false;  // KTH_HOOK_K16_TOPK_NOSKIP (tests): the count pass ignores the streaming pass's flags
     // timing: event pairs around the streaming pass and around whole selects
     bool timing = false;
     std::vector<hipEvent_t> ev_main, ev_total;
@@ -1099,6 +1105,7 @@ int kth_ctx_test_hook(kth_ctx *c, int hook, int64_t value) {
         return KTH_OK;
     case KTH_HOOK_K16_MISS: c->k16_miss = value != 0; return KTH_OK;
     case KTH_HOOK_FINISH_SLICES: c->finish_slices = value != 0; return KTH_OK;
+    case KTH_HOOK_K16_TOPK_NOSKIP: c->k16_topk_noskip = value != 0; return KTH_OK;
     default: return KTH_EINVAL;
     }
 }
@@ -1112,7 +1119,7 @@ int kth_ctx_destroy(kth_ctx *c) {
     if (c->st) (void)hipFree(c->st);
     if (c->islots) (void)hipFree(c->islots);
     release_all(c->sample, c->cand, c->gdir, c->cand_rows, c->tk_segv, c->tk_segp, c->tk_wcnt, c->tk_wstart, c->staging,
-                c->topk, c->mstate, c->mslots, c->mcand, c->k16, c->k16st);
+                c->topk, c->mstate, c->mslots, c->mcand, c->k16, c->k16st, c->tk16_nread);
     if (c->d_mstatus) (void)hipFree(c->d_mstatus);
     if (c->h_mstatus) (void)hipHostFree(c->h_mstatus);
     if (c->d_status) (void)hipFree(c->d_status);
@@ -1494,6 +1501,10 @@ template <int CV>
 const void *k16_main_fn() {
     return reinterpret_cast<const void *>(kth::k16_main<CV>);
 }
+template <int CV>
+const void *k16_main_tf_fn() {
+    return reinterpret_cast<const void *>(kth::k16_main_tf<CV>);
+}
 
 // Scratch of every k16 call, whatever n and m: the sample histogram, a set of
 // bins per rank and the states (~1.3 MB), the status words.
@@ -1511,13 +1522,18 @@ int reserve_k16(kth_ctx *c) {
         for (const void *f : hist) HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)K16_HIST_LDS));
         const void *mains[3] = {k16_main_fn<0>(), k16_main_fn<1>(), k16_main_fn<2>()};
         for (int v = 0; v < 3; ++v) c->k16_grid[v] = pass_grid(c, mains[v]);
+        const void *flagged[3] = {k16_main_tf_fn<0>(), k16_main_tf_fn<1>(), k16_main_tf_fn<2>()};
+        for (int v = 0; v < 3; ++v) c->k16_tf_grid[v] = pass_grid(c, flagged[v]);
         c->k16_ready = true;
     }
     return KTH_OK;
 }
 
+// tf (kth_topk_k16, D == 1): pass 0 is the flag-recording k16_main_tf; the
+// later passes, which return at once unless the window missed, stay unflagged.
 template <int CV>
-int run_k16(kth_ctx *c, const uint16_t *keys, int64_t n, const int64_t *dk, int D, int kind, const kth::K16Out &out) {
+int run_k16(kth_ctx *c, const uint16_t *keys, int64_t n, const int64_t *dk, int D, int kind, const kth::K16Out &out,
+            const kth::K16Flags *tf = nullptr) {
     const bool small = n <= kth::K16_SMALL_N;
     const int64_t s = small ? n : sample_size(n);
     const u64 nchunks = ((u64)s + kth::K16_CHUNK - 1) / kth::K16_CHUNK;
@@ -1554,7 +1570,10 @@ int run_k16(kth_ctx *c, const uint16_t *keys, int64_t n, const int64_t *dk, int 
         const kth::K16FinArgs fa{c->k16st.p, bins, top, out};
         for (int pass = 0; pass < kth::K16_PASSES; ++pass) {  // (the later ones return at once when every rank is settled)
             if (pass == 0) ev_main(c);
-            kth::k16_main<CV><<<c->k16_grid[CV], kth::BLK, 0, c->stream>>>(ma);
+            if (pass == 0 && tf)
+                kth::k16_main_tf<CV><<<c->k16_tf_grid[CV], kth::BLK, 0, c->stream>>>(ma, *tf);
+            else
+                kth::k16_main<CV><<<c->k16_grid[CV], kth::BLK, 0, c->stream>>>(ma);
             if (pass == 0) ev_main(c);
             kth::k16_finish<<<D, kth::K16_HIST_BLK, 0, c->stream>>>(fa);
         }
@@ -2021,9 +2040,133 @@ int topk_impl(kth_ctx *c, const int32_t *d_keys, int64_t n, int64_t k, int large
     return launch_check();
 }
 
+// ---------------------------------------------------- top-k of 16-bit keys
+// kth_topk_k16 (kth_topk16.hpp): the 16-bit select of rank k (largest: n - k +
+// 1) with one rank and no output, then count, k_topk_bases and write.  One
+// copy of the sequence, instantiated per ord transform and alignment.
+// The flagged streaming pass (k16_main_tf) is taken for k <= n / 16384, the
+// rule the 32-bit top-k's row flags started from scaled to this pass's
+// geometry: were every output key alone in its 2048-key row, at most an eighth
+// of the rows could hold output, and the count pass loads the rest of the
+// input a second time above it for little.  (Not yet moved by a measurement:
+// DESIGN.md "Top-k of one 16-bit array".)  Above it the unflagged k16_main
+// runs and the count pass reads every tile.
+constexpr u64 TK16_FLAG_FRAC = 16384;
+
+struct Tk16Plan {
+    u64 ntiles, nblk, pad, head, nfull;
+    bool tf;
+    u64 *toff, *bsum, *bbase, *meta, *nread;
+    uint32_t *tcnt, *hdr;
+};
+
+template <int CV, bool ALIGNED>
+int topk16_run(kth_ctx *c, const uint16_t *keys, int64_t n, int64_t k, int64_t rank, int largest, int kind,
+               const Tk16Plan &p, uint16_t *d_vals, int64_t *d_idx) {
+    int64_t dk[KTH_MULTI_MAX_RANKS];
+    int first[KTH_MULTI_MAX_RANKS];
+    const int D = distinct_ranks(c, &rank, 1, dk, first);  // one rank, set 0
+    kth::K16Out out;
+    memset(&out, 0, sizeof out);
+    out.m = 1;
+    out.kind = kind;
+    out.set[0] = c->multi_set[0];
+    const kth::K16Flags fl{p.hdr, largest ? 1u : 0u};
+    KTH_TRY(run_k16<CV>(c, keys, n, dk, D, kind, out, p.tf ? &fl : nullptr));
+    kth::K16State *st = c->k16st.p + c->multi_set[0];
+    const uint32_t nl = kth::k16_nl(kind), top = kth::k16_top(kind);
+    const kth::Tk16Args a{keys, (u64)n, p.pad, p.ntiles, st, largest ? 0xFFFFu : 0u, nl | nl << 16, top | top << 16, p.tcnt};
+    const kth::Tk16Skip sk{p.hdr, p.head, p.nfull, p.tf && !c->k16_topk_noskip ? 1u : 0u, p.nread};
+    const kth::Tk16Out o{p.toff, p.bbase, p.meta, st, kth::k16_float(kind) ? kth::k16_inf(kind) : 0xFFFFu,
+                         (uint32_t)kth::k16_bits_of_ord(top, kind), d_vals, d_idx};
+    // count and write passes: one wave per 64 tiles
+    const int waves = kth::TK_BLOCK / kth::WAVE;
+    const int g = (int)std::min<u64>((p.ntiles + waves * kth::WAVE - 1) / (waves * kth::WAVE), (u64)c->num_cu * 16);
+    HIP_TRY(hipMemsetAsync(p.nread, 0, sizeof(u64), c->stream));
+    kth::k16_topk_count<CV, ALIGNED><<<g, kth::TK_BLOCK, 0, c->stream>>>(a, sk);
+    // (a null SelState: k16_topk_write carries a bracket failure to the 16-bit state)
+    kth::k_topk_bases<<<(int)p.nblk, kth::TK_BLOCK, 0, c->stream>>>(
+        p.tcnt, p.ntiles, p.toff, p.bsum, (u64)k, p.bbase, p.meta, nullptr,
+        reinterpret_cast<uint32_t *>(c->islots + BAR_OFF) + kth::BAR_TOPK_ARRIVE);
+    kth::k16_topk_write<CV, ALIGNED><<<g, kth::TK_BLOCK, 0, c->stream>>>(a, o);
+    return launch_check();
+}
+
+int topk16_impl(kth_ctx *c, const void *d_keys, int64_t n, int64_t k, int largest, int kind, uint16_t *d_vals,
+                int64_t *d_idx) {
+    if (!c || !d_keys || (!d_vals && !d_idx) || n < 1 || k < 1 || k > n || kind < KTH_K16_I16 || kind > KTH_K16_BF16)
+        return KTH_EINVAL;
+    KTH_TRY(set_device(c));
+    KTH_TRY(reserve_k16(c));
+    const uint16_t *keys = static_cast<const uint16_t *>(d_keys);
+    Tk16Plan p;
+    // tiles in virtual indices: pad keys lie between the 16-byte boundary below d_keys and d_keys
+    p.pad = (reinterpret_cast<uintptr_t>(keys) & 15u) >> 1;
+    p.ntiles = ((u64)n + p.pad + kth::TK16_TILE - 1) / kth::TK16_TILE;
+    p.nblk = (p.ntiles + kth::TK_TILES_PER_BLOCK - 1) / kth::TK_TILES_PER_BLOCK;
+    // k16_main's geometry: its rows start after `head` unaligned keys
+    p.head = std::min<u64>((8 - p.pad) & 7, (u64)n);
+    p.nfull = (((u64)n - p.head) >> 3) / ((u64)kth::BLK * kth::K16_UNROLL);
+    p.tf = n > kth::K16_SMALL_N && (u64)k * TK16_FLAG_FRAC <= (u64)n;
+    // scratch (u64 words): offsets, block sums and bases, meta, the counts,
+    // then the flag header and a 32-bit word per k16_main tile
+    const u64 before = p.ntiles + 4 * p.nblk + 2 + (p.ntiles + 1) / 2;
+    const u64 fw64 = (4 + p.nfull + 1) / 2;
+    KTH_TRY(c->topk.reserve(before + fw64 + 2));
+    KTH_TRY(c->tk16_nread.reserve(2));
+    p.toff = c->topk.p;
+    p.bsum = p.toff + p.ntiles;
+    p.bbase = p.bsum + 2 * p.nblk;
+    p.meta = p.bbase + 2 * p.nblk;
+    p.nread = c->tk16_nread.p;
+    p.tcnt = reinterpret_cast<uint32_t *>(p.meta + 2);
+    p.hdr = reinterpret_cast<uint32_t *>(c->topk.p + before);
+    if (c->k16_dirty) {
+        HIP_TRY(hipMemsetAsync(c->k16.p, 0, c->k16.count * sizeof(u64), c->stream));
+        c->k16_dirty = false;
+    }
+    // the k-th smallest (largest: the (n-k+1)-th smallest) -> K16State[0].answer, on the device
+    int64_t rank = largest ? n - k + 1 : k;
+    if (c->fault_topk_rank && n > 1) rank = rank < n ? rank + 1 : rank - 1;
+    const bool aligned = p.pad == 0;
+    ev_mark(c, c->ev_total, c->total_used);
+    int rc;
+    switch ((kind == KTH_K16_U16 ? 0 : kind == KTH_K16_I16 ? 1 : 2) * 2 + (aligned ? 1 : 0)) {
+    case 0: rc = topk16_run<0, false>(c, keys, n, k, rank, largest, kind, p, d_vals, d_idx); break;
+    case 1: rc = topk16_run<0, true>(c, keys, n, k, rank, largest, kind, p, d_vals, d_idx); break;
+    case 2: rc = topk16_run<1, false>(c, keys, n, k, rank, largest, kind, p, d_vals, d_idx); break;
+    case 3: rc = topk16_run<1, true>(c, keys, n, k, rank, largest, kind, p, d_vals, d_idx); break;
+    case 4: rc = topk16_run<2, false>(c, keys, n, k, rank, largest, kind, p, d_vals, d_idx); break;
+    default: rc = topk16_run<2, true>(c, keys, n, k, rank, largest, kind, p, d_vals, d_idx); break;
+    }
+    ev_mark(c, c->ev_total, c->total_used);
+    if (rc != KTH_OK) {
+        c->k16_dirty = true;
+        return rc;
+    }
+    c->tk16_tiles = p.ntiles;
+    return KTH_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int kth_topk_k16(kth_ctx *c, const void *d_keys, int64_t n, int64_t k, int largest, int kind, uint16_t *d_vals,
+                 int64_t *d_idx) {
+    return topk16_impl(c, d_keys, n, k, largest, kind, d_vals, d_idx);
+}
+
+int kth_ctx_last_topk_k16_tiles(kth_ctx *c, uint64_t *tiles, uint64_t *tiles_read) {
+    if (!c || !tiles || !tiles_read || c->tk16_tiles == 0) return KTH_EINVAL;  // no kth_topk_k16 yet
+    KTH_TRY(set_device(c));
+    u64 *h = reinterpret_cast<u64 *>(c->h_state);  // pinned
+    HIP_TRY(hipMemcpyAsync(h, c->tk16_nread.p, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *tiles = c->tk16_tiles;
+    *tiles_read = *h;
+    return KTH_OK;
+}
 
 int kth_topk_i32(kth_ctx *c, const int32_t *d_keys, int64_t n, int64_t k, int largest, int32_t *d_vals,
                  int64_t *d_idx) {

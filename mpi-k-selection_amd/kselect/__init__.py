@@ -44,6 +44,7 @@ from ._lib import (  # noqa: F401
     KTH_HOOK_FAULT_TOPK_RANK,
     KTH_HOOK_FINISH_SLICES,
     KTH_HOOK_K16_MISS,
+    KTH_HOOK_K16_TOPK_NOSKIP,
     KTH_HOOK_TOPK_SEG_CAP,
     KTH_MULTI_MAX_RANKS,
     KTH_K16_BF16,
@@ -426,6 +427,31 @@ class Selector:
         check(fn(self._ctx, _ptr(d_keys), int(n), int(k), 1 if largest else 0,
                  _ptr(d_vals) if d_vals is not None else None,
                  _ptr(d_idx) if d_idx is not None else None), what)
+
+    def topk16(self, d_keys, n, k, d_vals=None, d_idx=None, largest=False, kind=None):
+        """The k smallest (largest=True: largest) of n 16-bit device keys and their
+        int64 indices, in index order, ties broken by index (kth_topk_k16;
+        asynchronous on the ctx stream).  `kind` as _k16_kind; d_vals: k 2-byte
+        elements of the keys' kind (a NaN canonical), d_idx: k int64; either may
+        be None, not both.  Nothing is converted."""
+        kind = _k16_kind(d_keys, kind, "d_keys")
+        if d_vals is not None:
+            _k16_same_kind(d_keys, d_vals, kind, "d_vals")
+        dt = getattr(d_idx, "dtype", None)
+        if dt is not None and str(dt).rsplit(".", 1)[-1] != "int64":
+            raise TypeError(f"d_idx must be int64, got {dt}")
+        check(LIB.kth_topk_k16(self._ctx, _ptr(d_keys), int(n), int(k), 1 if largest else 0, kind,
+                               _ptr(d_vals) if d_vals is not None else None,
+                               _ptr(d_idx) if d_idx is not None else None), "kth_topk_k16")
+
+    def topk16_tiles(self):
+        """(tiles, tiles_read) of the last topk16: its count-pass tiles and how
+        many of them were loaded from the input (kth_ctx_last_topk_k16_tiles;
+        synchronises)."""
+        tiles, read = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        check(LIB.kth_ctx_last_topk_k16_tiles(self._ctx, ctypes.byref(tiles), ctypes.byref(read)),
+              "kth_ctx_last_topk_k16_tiles")
+        return tiles.value, read.value
 
     def fill(self, d_out, n, family=UNIFORM_FULL, seed=DEFAULT_SEED, param=0, offset=0, n_total=None):
         if isinstance(family, str):

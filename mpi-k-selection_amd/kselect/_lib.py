@@ -33,6 +33,7 @@ KTH_MULTI_MAX_RANKS = 8
 KTH_HOOK_FAULT_TOPK_RANK, KTH_HOOK_FAULT_BARRIER, KTH_HOOK_TOPK_SEG_CAP = 1, 2, 3
 KTH_HOOK_K16_MISS = 4
 KTH_HOOK_FINISH_SLICES = 5
+KTH_HOOK_K16_TOPK_NOSKIP = 6
 # kth_ctx_last_finish_form: how the cooperative finish of the last select ended
 KTH_FINISH_NONE, KTH_FINISH_COUNTS, KTH_FINISH_SLICES, KTH_FINISH_GROUPED, KTH_FINISH_LEVELS = range(5)
 
@@ -137,6 +138,8 @@ PROTOS = {
                                          ctypes.c_int, c_vp, c_vp]),
     "kth_topk_i32": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, c_vp, c_vp]),
     "kth_topk_f32": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, c_vp, c_vp]),
+    "kth_topk_k16": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
+    "kth_ctx_last_topk_k16_tiles": (ctypes.c_int, [c_vp, c_u64p, c_u64p]),
     "kth_fill_synthetic": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                           ctypes.c_uint64, ctypes.c_int32]),
     "kth_dist_begin": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64]),
