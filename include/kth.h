@@ -450,6 +450,63 @@ int kth_topk_k16(kth_ctx *ctx, const void *d_keys, int64_t n, int64_t k, int lar
  * call. */
 int kth_ctx_last_topk_k16_tiles(kth_ctx *ctx, uint64_t *tiles, uint64_t *tiles_read);
 
+/* --- wide rows: k-th and top-k per row of up to 2^24 columns -------------------
+ * kth_select_rows_* and kth_topk_rows_* for the shape between them and the
+ * one-array calls: a batch of 1 to a few thousand rows of 32 Ki to 1 Mi int32
+ * or float32 keys (a logits matrix, a quantile per long channel).  Row r is
+ * d_keys[r*ld .. r*ld + cols), ld >= cols in elements (a padded vocabulary, a
+ * column view).  1 <= k <= cols <= KTH_WIDE_MAX_COLS; rows >= 0, rows == 0
+ * returns KTH_OK and launches nothing.  Any cols, ld and base alignment is
+ * exact; the fast case is a 16-byte aligned base with ld % 4 == 0 (16-byte
+ * loads), anything else takes guarded 4-byte loads.
+ * Order and results are exactly those of kth_select_rows_* / kth_topk_rows_*:
+ * int32 in signed order, float32 in IEEE total order (-0.0 < +0.0, subnormals
+ * distinct, every NaN equal to every other and above +inf); a value written
+ * has the bit pattern of an input element, a NaN is written as 0x7FC00000.
+ * Top-k: the k smallest keys (largest != 0: the k largest) with their int32
+ * columns, in column order; of the keys equal to the k-th, the first ones by
+ * column.  d_vals, d_idx: dense rows x k, either may be NULL, not both.  For
+ * cols in the existing calls' ranges the outputs are bit-identical to theirs.
+ * Asynchronous on the ctx stream, device memory only, no host synchronisation;
+ * no allocation once kth_ctx_reserve_wide_rows(ctx, rows, cols) or an earlier
+ * call of that shape has run; graph-capturable under the conditions written at
+ * kth_select_i32_async (a forced plan is frozen at capture).  The calls use
+ * scratch of their own in the ctx, which every launch sequence leaves as it
+ * found it, and touch no other ctx buffer nor the last-call word: any eager
+ * call or replay may precede or follow, and kth_ctx_last_stats is unaffected.
+ * KTH_EINVAL before any device work, outputs untouched: a NULL ctx or keys, no
+ * output pointer, rows < 0, a bad cols, ld or k.  KTH_ENODEV without a GPU.
+ * Two forms, chosen by kth_wide_rows_plan from (rows, cols, num_cu)
+ * (csrc/kth_rows_wide.hpp): `slices` workgroups share a row when the rows
+ * alone do not fill the GPU (a radix select of at most three digits, the
+ * row's histogram in scratch, every hand-off a kernel boundary); slices == 1
+ * is one workgroup per row with every digit in one launch.  Rows are
+ * processed in groups of group_rows, so the scratch (scratch_bytes of the
+ * plan, 0 for slices == 1) stays at or below 32 MiB whatever rows is;
+ * slice_keys (a multiple of 4) is the columns of a slice. */
+#define KTH_WIDE_MAX_COLS   (1 << 24)
+#define KTH_WIDE_MAX_SLICES 256
+int kth_select_wide_rows_i32(kth_ctx *ctx, const int32_t *d_keys, int64_t rows, int32_t cols, int64_t ld, int32_t k,
+                             int32_t *d_out);
+int kth_select_wide_rows_f32(kth_ctx *ctx, const float *d_keys, int64_t rows, int32_t cols, int64_t ld, int32_t k,
+                             float *d_out);
+int kth_topk_wide_rows_i32(kth_ctx *ctx, const int32_t *d_keys, int64_t rows, int32_t cols, int64_t ld, int32_t k,
+                           int largest, int32_t *d_vals, int32_t *d_idx);
+int kth_topk_wide_rows_f32(kth_ctx *ctx, const float *d_keys, int64_t rows, int32_t cols, int64_t ld, int32_t k,
+                           int largest, float *d_vals, int32_t *d_idx);
+/* Pre-size the scratch for wide-rows calls of up to `rows` rows (whatever plan,
+ * forced ones included, they take). */
+int kth_ctx_reserve_wide_rows(kth_ctx *ctx, int64_t rows, int32_t cols);
+/* The automatic plan.  Host arithmetic only, no device needed; any output
+ * pointer may be NULL.  KTH_EINVAL: rows < 0, a bad cols, num_cu < 1. */
+int kth_wide_rows_plan(int64_t rows, int32_t cols, int num_cu, int32_t *slices, int32_t *slice_keys,
+                       int32_t *group_rows, int64_t *scratch_bytes);
+/* Tests and tuning: force the plan of this ctx; 0 = automatic for that field
+ * (slices == 1 forces the fused form; more slices than cols / 4 allows, or
+ * more group_rows than the scratch bound, are cut down).  KTH_EINVAL: a NULL
+ * ctx, a negative value, slices > KTH_WIDE_MAX_SLICES. */
+int kth_ctx_wide_rows_force(kth_ctx *ctx, int32_t slices, int32_t group_rows);
+
 /* --- synthetic inputs (bench / tests) --------------------------------------
  * Fills d_out[0..n) with the keys of global indices offset..offset+n of an
  * n_total-key input of family `dist` (oracle/kth_oracle.h enum ko_dist;

@@ -205,6 +205,13 @@ struct kth_ctx {
     u64 tk16_tiles = 0;
     DevBuf<u64> tk16_nread;        // ... and the tiles its count pass loaded from the input
     bool k16_topk_noskip = false;  // KTH_HOOK_K16_TOPK_NOSKIP (tests): the count pass ignores the streaming pass's flags
+    // wide rows, split form: a histogram and a state per row of a group (zero between
+    // calls but for the state's overwritten words), (better, equal) per slice
+    DevBuf<uint32_t> wide_hist;
+    DevBuf<kth::WideState> wide_state;
+    DevBuf<uint32_t> wide_cnt;
+    bool wide_dirty = false;   // a wide-rows sequence was cut short: re-zero its scratch
+    int32_t wide_force_slices = 0, wide_force_group = 0;  // kth_ctx_wide_rows_force (0: automatic)
     // timing: event pairs around the streaming pass and around whole selects
     bool timing = false;
     std::vector<hipEvent_t> ev_main, ev_total;
@@ -878,6 +885,131 @@ int rows16_entry(kth_ctx *c, const void *d_keys, int64_t rows, int32_t cols, int
                                 : launch_rows16<false, TOPK>(c, keys, rows, cols, k, kind, flip, d_out, d_vals, d_idx);
 }
 
+// Wide rows (kth_rows_wide.hpp).  The plan: how many workgroups share a row
+// (slices; 1 = the fused one-workgroup-per-row kernel), the columns of a slice,
+// and how many rows one launch sequence takes (group_rows, which bounds the
+// scratch whatever `rows` is).
+static_assert(KTH_WIDE_MAX_SLICES == kth::WD_MAX_SLICES, "include/kth.h wide-rows slice limit");
+constexpr int64_t WIDE_SCRATCH_MAX = (int64_t)32 << 20;
+// scratch bytes a row of a group: its histogram, its state, and (better, equal)
+// for KTH_WIDE_MAX_SLICES slices, so that no forced plan needs more than a
+// reserve of the same rows gave
+constexpr int64_t WIDE_ROW_BYTES = 4 * ((int64_t)kth::NBINS + kth::WD_STATE_WORDS + 2 * kth::WD_MAX_SLICES);
+constexpr int64_t WIDE_GROUP_MAX = WIDE_SCRATCH_MAX / WIDE_ROW_BYTES;  // 3266 rows: also below the grid's y limit
+constexpr int64_t WIDE_FUSED_GROUP_MAX = 1 << 16;  // the fused form has no scratch: rows a launch
+// Automatic plan (DESIGN.md "Wide rows", from profiles/rows_wide_plan_sweep.jsonl):
+// the fused form when the rows alone fill the GPU (rows >= WIDE_FUSED_ROWS_PER_CU
+// * num_cu) or a row is short enough for one workgroup to read it three times
+// within the split sequence's launch-bound floor (cols <= WIDE_FUSED_COLS);
+// else rows are split until the grid holds WIDE_WG_PER_CU workgroups a CU, a
+// slice keeping at least WIDE_MIN_SLICE columns (a workgroup's fixed cost, its
+// histogram cleared and 2048 bins flushed, is not worth fewer keys).
+// Fewer than WIDE_MIN_SLICES slices never beat the fused form.
+constexpr int WIDE_WG_PER_CU = 4;
+constexpr int WIDE_FUSED_ROWS_PER_CU = 2;
+constexpr int32_t WIDE_FUSED_COLS = 32768;
+constexpr int32_t WIDE_MIN_SLICE = 4096;
+constexpr int32_t WIDE_MIN_SLICES = 4;
+
+struct WidePlan {
+    int32_t slices, slice_keys, group_rows;
+    int64_t scratch_bytes;
+};
+
+WidePlan wide_plan(int64_t rows, int32_t cols, int num_cu, int32_t force_slices, int32_t force_group) {
+    int64_t want = force_slices;
+    if (want <= 0) {
+        if (rows <= 0 || rows >= (int64_t)WIDE_FUSED_ROWS_PER_CU * num_cu || cols <= WIDE_FUSED_COLS) {
+            want = 1;
+        } else {
+            want = std::min<int64_t>((int64_t)WIDE_WG_PER_CU * num_cu / rows, cols / WIDE_MIN_SLICE);
+            if (want < WIDE_MIN_SLICES) want = 1;
+        }
+    }
+    want = std::max<int64_t>(1, std::min<int64_t>(want, KTH_WIDE_MAX_SLICES));
+    WidePlan p;
+    p.slice_keys = (int32_t)(((cols + want - 1) / want + 3) & ~(int64_t)3);
+    p.slices = (cols + p.slice_keys - 1) / p.slice_keys;  // (the last slice is never empty)
+    int64_t g = std::min(std::max<int64_t>(rows, 1), p.slices > 1 ? WIDE_GROUP_MAX : WIDE_FUSED_GROUP_MAX);
+    if (force_group > 0) g = std::min<int64_t>(g, force_group);
+    p.group_rows = (int32_t)g;
+    p.scratch_bytes = p.slices > 1 ? g * WIDE_ROW_BYTES : 0;
+    return p;
+}
+
+// The split form's scratch for groups of g rows; new buffers are zeroed.
+int reserve_wide(kth_ctx *c, int64_t g) {
+    const u64 had_hist = c->wide_hist.count, had_state = c->wide_state.count;
+    int rc = c->wide_hist.reserve((u64)g * kth::NBINS);
+    if (rc == KTH_OK) rc = c->wide_state.reserve((u64)g);
+    if (rc == KTH_OK) rc = c->wide_cnt.reserve((u64)g * 2 * kth::WD_MAX_SLICES);
+    if (rc != KTH_OK) {
+        release_all(c->wide_hist, c->wide_state, c->wide_cnt);
+        return rc;
+    }
+    if (c->wide_hist.count != had_hist || c->wide_dirty)
+        HIP_TRY(hipMemsetAsync(c->wide_hist.p, 0, c->wide_hist.count * sizeof(uint32_t), c->stream));
+    if (c->wide_state.count != had_state || c->wide_dirty)
+        HIP_TRY(hipMemsetAsync(c->wide_state.p, 0, c->wide_state.count * sizeof(kth::WideState), c->stream));
+    c->wide_dirty = false;
+    return KTH_OK;
+}
+
+// One group of g rows: the fused launch, or the split form's sequence -- per
+// digit a count and a pick, for the top-k a count per slice and the compaction.
+template <bool F32, bool VEC, bool TOPK>
+int launch_wide_group(kth_ctx *c, const WidePlan &p, const uint32_t *keys, int64_t g, uint32_t cols, u64 ld, uint32_t k,
+                      uint32_t flip, uint32_t *out, uint32_t *vals, int32_t *idx) {
+    if (p.slices == 1) {
+        kth::k_wide_fused<F32, VEC, TOPK><<<(int)g, kth::WD_FBLOCK, 0, c->stream>>>(keys, ld, cols, k, flip, out, vals, idx);
+        return launch_check();
+    }
+    const dim3 grid((unsigned)p.slices, (unsigned)g);
+    const uint32_t sk = (uint32_t)p.slice_keys;
+    for (int pass = 0; pass < 3; ++pass) {
+        kth::k_wide_count<F32, VEC><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, flip, pass, c->wide_hist.p,
+                                                                        c->wide_state.p);
+        kth::k_wide_pick<F32><<<(int)g, kth::WD_BLOCK, 0, c->stream>>>(c->wide_hist.p, c->wide_state.p, pass, cols, k, flip,
+                                                                    TOPK ? nullptr : out);
+    }
+    if (TOPK) {
+        kth::k_wide_tk_count<F32, VEC><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, flip, c->wide_state.p,
+                                                                           c->wide_cnt.p);
+        kth::k_wide_tk_write<F32, VEC><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, flip, k, c->wide_state.p,
+                                                                           c->wide_cnt.p, vals, idx);
+    }
+    const int rc = launch_check();
+    if (rc != KTH_OK) c->wide_dirty = true;
+    return rc;
+}
+
+// The four wide-rows entry points: the argument check, the plan, the scratch
+// and the loop over row groups.
+template <bool F32, bool TOPK>
+int wide_rows_entry(kth_ctx *c, const void *d_keys, int64_t rows, int32_t cols, int64_t ld, int32_t k, void *d_out,
+                    int largest = 0, void *d_vals = nullptr, int32_t *d_idx = nullptr) {
+    const bool has_out = TOPK ? d_vals || d_idx : d_out != nullptr;
+    if (!c || !d_keys || !has_out || rows < 0 || cols < 1 || cols > KTH_WIDE_MAX_COLS || ld < cols || k < 1 || k > cols)
+        return KTH_EINVAL;
+    if (rows == 0) return KTH_OK;
+    KTH_TRY(set_device(c));
+    const WidePlan p = wide_plan(rows, cols, c->num_cu, c->wide_force_slices, c->wide_force_group);
+    if (p.slices > 1) KTH_TRY(reserve_wide(c, p.group_rows));
+    const uint32_t *keys = static_cast<const uint32_t *>(d_keys);
+    uint32_t *out = static_cast<uint32_t *>(d_out), *vals = static_cast<uint32_t *>(d_vals);
+    const bool vec = (reinterpret_cast<uintptr_t>(keys) & 15u) == 0 && ld % 4 == 0;
+    const uint32_t flip = TOPK && largest ? 0xFFFFFFFFu : 0u;
+    for (int64_t r0 = 0; r0 < rows; r0 += p.group_rows) {
+        const int64_t g = std::min<int64_t>(p.group_rows, rows - r0);
+        const uint32_t *gk = keys + (u64)r0 * (u64)ld;
+        uint32_t *go = out ? out + r0 : nullptr, *gv = vals ? vals + (u64)r0 * (u64)k : nullptr;
+        int32_t *gi = d_idx ? d_idx + (u64)r0 * (u64)k : nullptr;
+        const auto launch = vec ? launch_wide_group<F32, true, TOPK> : launch_wide_group<F32, false, TOPK>;
+        KTH_TRY(launch(c, p, gk, g, (uint32_t)cols, (u64)ld, (uint32_t)k, flip, go, gv, gi));
+    }
+    return KTH_OK;
+}
+
 // ------------------------------------------------------- ctx creation, in parts
 // Every tuning variable of a ctx (design exploration and A/B runs; unset: the
 // defaults in kth_ctx).  Needs c->num_cu.  Read elsewhere: KTH_STAMPS (the
@@ -1119,7 +1251,8 @@ int kth_ctx_destroy(kth_ctx *c) {
     if (c->st) (void)hipFree(c->st);
     if (c->islots) (void)hipFree(c->islots);
     release_all(c->sample, c->cand, c->gdir, c->cand_rows, c->tk_segv, c->tk_segp, c->tk_wcnt, c->tk_wstart, c->staging,
-                c->topk, c->mstate, c->mslots, c->mcand, c->k16, c->k16st, c->tk16_nread);
+                c->topk, c->mstate, c->mslots, c->mcand, c->k16, c->k16st, c->tk16_nread, c->wide_hist, c->wide_state,
+                c->wide_cnt);
     if (c->d_mstatus) (void)hipFree(c->d_mstatus);
     if (c->h_mstatus) (void)hipHostFree(c->h_mstatus);
     if (c->d_status) (void)hipFree(c->d_status);
@@ -1905,6 +2038,51 @@ int kth_select_rows_k16(kth_ctx *c, const void *d_keys, int64_t rows, int32_t co
 int kth_topk_rows_k16(kth_ctx *c, const void *d_keys, int64_t rows, int32_t cols, int32_t k, int largest, int kind,
                       uint16_t *d_vals, int32_t *d_idx) {
     return rows16_entry<true>(c, d_keys, rows, cols, k, kind, nullptr, largest, d_vals, d_idx);
+}
+
+int kth_select_wide_rows_i32(kth_ctx *c, const int32_t *d_keys, int64_t rows, int32_t cols, int64_t ld, int32_t k,
+                             int32_t *d_out) {
+    return wide_rows_entry<false, false>(c, d_keys, rows, cols, ld, k, d_out);
+}
+
+int kth_select_wide_rows_f32(kth_ctx *c, const float *d_keys, int64_t rows, int32_t cols, int64_t ld, int32_t k,
+                             float *d_out) {
+    return wide_rows_entry<true, false>(c, d_keys, rows, cols, ld, k, d_out);
+}
+
+int kth_topk_wide_rows_i32(kth_ctx *c, const int32_t *d_keys, int64_t rows, int32_t cols, int64_t ld, int32_t k,
+                           int largest, int32_t *d_vals, int32_t *d_idx) {
+    return wide_rows_entry<false, true>(c, d_keys, rows, cols, ld, k, nullptr, largest, d_vals, d_idx);
+}
+
+int kth_topk_wide_rows_f32(kth_ctx *c, const float *d_keys, int64_t rows, int32_t cols, int64_t ld, int32_t k,
+                           int largest, float *d_vals, int32_t *d_idx) {
+    return wide_rows_entry<true, true>(c, d_keys, rows, cols, ld, k, nullptr, largest, d_vals, d_idx);
+}
+
+int kth_ctx_reserve_wide_rows(kth_ctx *c, int64_t rows, int32_t cols) {
+    if (!c || rows < 0 || cols < 1 || cols > KTH_WIDE_MAX_COLS) return KTH_EINVAL;
+    KTH_TRY(set_device(c));
+    // for the split form whatever the plan of (rows, cols) is: a forced plan then fits too
+    return reserve_wide(c, std::min(std::max<int64_t>(rows, 1), WIDE_GROUP_MAX));
+}
+
+int kth_wide_rows_plan(int64_t rows, int32_t cols, int num_cu, int32_t *slices, int32_t *slice_keys,
+                       int32_t *group_rows, int64_t *scratch_bytes) {
+    if (rows < 0 || cols < 1 || cols > KTH_WIDE_MAX_COLS || num_cu < 1) return KTH_EINVAL;
+    const WidePlan p = wide_plan(rows, cols, num_cu, 0, 0);
+    if (slices) *slices = p.slices;
+    if (slice_keys) *slice_keys = p.slice_keys;
+    if (group_rows) *group_rows = p.group_rows;
+    if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
+    return KTH_OK;
+}
+
+int kth_ctx_wide_rows_force(kth_ctx *c, int32_t slices, int32_t group_rows) {
+    if (!c || slices < 0 || group_rows < 0 || slices > KTH_WIDE_MAX_SLICES) return KTH_EINVAL;
+    c->wide_force_slices = slices;
+    c->wide_force_group = group_rows;
+    return KTH_OK;
 }
 
 }  // extern "C"

@@ -1,0 +1,406 @@
+// kth_rows_wide.hpp -- per-row k-th selection and top-k for wide rows (up to
+// 2^24 columns of int32 or float32 keys; include/kth.h "wide rows"): the shape
+// between the one-array calls and the register / LDS rows kernels, a batch of
+// 1 to a few thousand rows of 32 Ki to 1 Mi columns (the logits matrix).
+//
+// An exact radix select on the 32-bit order key, three digits at most
+// (11 + 11 + 10 bits, <= 2048 bins), in two forms (kth_wide_rows_plan):
+//
+//   split (slices > 1): too few rows to fill the GPU, so `slices` workgroups
+//     share a row (grid slices x group_rows).  Per digit, k_wide_count has each
+//     workgroup histogram its slice in LDS and add its non-empty bins to the
+//     row's 8 KiB histogram in scratch; k_wide_pick (one workgroup a row) picks
+//     the digit after the kernel boundary, advances the row's state and clears
+//     the histogram.  Every hand-off between workgroups is a kernel boundary: no
+//     cooperative launch, no grid barrier, no in-launch flag.
+//   fused (slices == 1): rows alone fill the GPU.  One workgroup per row runs
+//     every digit in one launch, histogram and pick in LDS behind workgroup
+//     barriers, no global atomics; the later digits re-read the row (from L2).
+//
+// Early end: every counting pass also takes the min and max of the keys that
+// match the prefix.  When they are equal the picked bin holds one value (one
+// key, or many equal ones) and that value is the answer: the remaining digits
+// are skipped (their launches return at once in the split form).
+//
+// The first digit of a float row is sign + exponent + two mantissa bits: a
+// randn row puts most keys into about ten bins, and a wave's LDS adds to one
+// address serialise.  The remedy of k_rows_reg and the 16-bit rows, WD_COPIES
+// histogram copies with lane % WD_COPIES picking one (exact for any input, the
+// copies summed at the flush / pick), was measured here and lost: 2 and 4
+// copies gain nothing on randn rows in either form and cost a split-form
+// workgroup its larger clear and flush (DESIGN.md "Wide rows").  One copy is
+// the default; KTH_WIDE_COPIES rebuilds the others.
+//
+// Top-k: the select leaves the k-th key and the tie quota (k minus the keys
+// strictly better).  Split: k_wide_tk_count writes (better, equal) per slice,
+// k_wide_tk_write derives each workgroup's output offset and its share of the
+// quota from the slices before it (<= 256 numbers) and compacts its slice in
+// column order.  Fused: the one workgroup walks the row with a running offset.
+// `flip` = 0xFFFFFFFF reverses the order key for the k largest.
+//
+// Loads: VEC = a 16-byte aligned base and ld % 4 == 0, so every row and every
+// slice starts on a 16-byte boundary and is read with 16-byte loads, the last
+// partial vector of a row by guarded 4-byte loads; otherwise guarded 4-byte
+// loads throughout.  A word becomes an order key right after its load
+// (WideKey: the one place that knows the key type; 16-bit wide rows would add
+// a trait here and leave the passes alone).
+// Included by kth_kernels.hip after kth_rows16.hpp.
+#pragma once
+
+namespace kth {
+
+#ifndef KTH_WIDE_COPIES
+#define KTH_WIDE_COPIES 1  // LDS histogram copies per workgroup (a power of two)
+#endif
+constexpr int WD_COPIES = KTH_WIDE_COPIES;
+static_assert((WD_COPIES & (WD_COPIES - 1)) == 0, "lane % WD_COPIES is a mask");
+constexpr int WD_BLOCK = 256;    // split-form kernels
+constexpr int WD_FBLOCK = 512;   // fused kernel: one workgroup per row
+constexpr int WD_U = 4;          // 16-byte loads in flight per thread in the counting passes
+constexpr int WD_MAX_SLICES = 256;
+static_assert(WD_MAX_SLICES <= WD_BLOCK, "k_wide_tk_write reads one slice's counts per thread");
+
+// The order key of a word and back (uint32, unsigned order = key order).
+template <bool F32>
+struct WideKey {
+    static __device__ __forceinline__ uint32_t key(uint32_t bits) { return F32 ? key_of_f32(bits) : key_of_i32(bits); }
+    static __device__ __forceinline__ uint32_t bits(uint32_t key) { return (uint32_t)out_word<F32>(key); }
+};
+
+// A row's selection state (split form; scratch).  nmn / mx accumulate max(~key)
+// and max(key) of the keys matching the prefix: zero is the identity of both,
+// and every pick leaves them zero.
+struct WideState {
+    uint32_t kk;      // remaining 1-based rank among the keys matching `prefix`; at the end the tie quota
+    uint32_t prefix;  // the digits picked so far, right-aligned
+    uint32_t done;
+    uint32_t answer;  // the k-th key (flipped order key)
+    uint32_t eqn;     // keys in the picked bin; at the end the keys equal to the answer
+    uint32_t nmn, mx;
+    uint32_t pad;
+};
+constexpr int WD_STATE_WORDS = sizeof(WideState) / 4;
+
+// digit `pass` of a key: bits [shift, shift + 11) (the last digit: the low 10)
+__device__ __forceinline__ uint32_t wd_shift(int pass) { return pass == 0 ? 21u : pass == 1 ? 10u : 0u; }
+__device__ __forceinline__ uint32_t wd_bins(int pass) { return pass == 2 ? 1024u : (uint32_t)NBINS; }
+
+// The words of columns e .. e+3 of a row; columns at or past `end` read as 0
+// and are never loaded.
+template <bool VEC>
+__device__ __forceinline__ uint4 wd_load4(const uint32_t *__restrict__ row, uint32_t e, uint32_t end) {
+    if (VEC && e + 4u <= end) return *reinterpret_cast<const uint4 *>(row + e);
+    uint4 x = make_uint4(0u, 0u, 0u, 0u);
+    if (e < end) x.x = row[e];
+    if (e + 1u < end) x.y = row[e + 1u];
+    if (e + 2u < end) x.z = row[e + 2u];
+    if (e + 3u < end) x.w = row[e + 3u];
+    return x;
+}
+
+__device__ __forceinline__ void wd_add(uint32_t *h, uint32_t bin) {
+    (void)__hip_atomic_fetch_add(h + bin, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+__device__ __forceinline__ uint32_t wd_wave_max(uint32_t x) {
+#pragma unroll
+    for (int o = WAVE / 2; o > 0; o >>= 1) {
+        const uint32_t y = (uint32_t)__shfl_xor((int)x, o, WAVE);
+        x = y > x ? y : x;
+    }
+    return x;
+}
+__device__ __forceinline__ uint32_t wd_wave_sum(uint32_t x) {
+#pragma unroll
+    for (int o = WAVE / 2; o > 0; o >>= 1) x += (uint32_t)__shfl_xor((int)x, o, WAVE);
+    return x;
+}
+
+// Digit `pass` of the keys of columns [begin, end) that match `prefix`, counted
+// into the workgroup's LDS copies `hist`; smm[0 .. 1] take max(~key), max(key)
+// of those keys.  The caller zeroes hist and smm before and synchronises after.
+template <bool F32, bool VEC, int BLOCK>
+__device__ __forceinline__ void wd_count_range(const uint32_t *__restrict__ row, uint32_t begin, uint32_t end,
+                                               uint32_t flip, int pass, uint32_t prefix, uint32_t *hist,
+                                               uint32_t *smm) {
+    uint32_t *mine = hist + (threadIdx.x & (WD_COPIES - 1)) * NBINS;
+    const uint32_t mshift = pass == 1 ? 21u : 10u, dshift = wd_shift(pass), dmask = wd_bins(pass) - 1u;
+    uint32_t nmn = 0, mx = 0;
+    for (uint32_t base = begin + threadIdx.x * 4u; base < end; base += (uint32_t)(BLOCK * 4 * WD_U)) {
+        uint4 x[WD_U];
+#pragma unroll
+        for (int u = 0; u < WD_U; ++u) x[u] = wd_load4<VEC>(row, base + (uint32_t)(u * BLOCK * 4), end);
+#pragma unroll
+        for (int u = 0; u < WD_U; ++u) {
+            const uint32_t e = base + (uint32_t)(u * BLOCK * 4);
+            const uint32_t w[4] = {x[u].x, x[u].y, x[u].z, x[u].w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t kx = WideKey<F32>::key(w[j]) ^ flip;
+                if (e + (uint32_t)j < end && (pass == 0 || (kx >> mshift) == prefix)) {
+                    wd_add(mine, (kx >> dshift) & dmask);
+                    nmn = ~kx > nmn ? ~kx : nmn;
+                    mx = kx > mx ? kx : mx;
+                }
+            }
+        }
+    }
+    nmn = wd_wave_max(nmn);
+    mx = wd_wave_max(mx);
+    if ((threadIdx.x & (WAVE - 1)) == 0) {
+        (void)__hip_atomic_fetch_max(smm, nmn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        (void)__hip_atomic_fetch_max(smm + 1, mx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+}
+
+template <int BLOCK>
+__device__ __forceinline__ void wd_zero_lds(uint32_t *hist, uint32_t *smm) {
+    for (int i = threadIdx.x; i < WD_COPIES * NBINS; i += BLOCK) hist[i] = 0u;
+    if (threadIdx.x < 2) smm[threadIdx.x] = 0u;
+}
+__device__ __forceinline__ uint32_t wd_bin_sum(const uint32_t *hist, uint32_t bin) {
+    uint32_t s = 0;
+#pragma unroll
+    for (int c = 0; c < WD_COPIES; ++c) s += hist[c * NBINS + bin];
+    return s;
+}
+
+// ---- split form: one digit of one slice
+template <bool F32, bool VEC>
+__global__ __launch_bounds__(WD_BLOCK, 4) void k_wide_count(const uint32_t *__restrict__ keys, u64 ld, uint32_t cols,
+                                                            uint32_t slice_keys, uint32_t flip, int pass,
+                                                            uint32_t *__restrict__ hist_g, WideState *__restrict__ st_g) {
+    __shared__ uint32_t hist[WD_COPIES * NBINS];
+    __shared__ uint32_t smm[2];
+    const uint32_t r = blockIdx.y, s = blockIdx.x;
+    WideState *st = st_g + r;
+    uint32_t prefix = 0;
+    if (pass > 0) {
+        if (st->done) return;  // (workgroup-uniform) settled by an earlier digit
+        prefix = st->prefix;
+    }
+    wd_zero_lds<WD_BLOCK>(hist, smm);
+    __syncthreads();
+    const uint32_t begin = s * slice_keys, end = begin + slice_keys < cols ? begin + slice_keys : cols;
+    wd_count_range<F32, VEC, WD_BLOCK>(keys + (u64)r * ld, begin, end, flip, pass, prefix, hist, smm);
+    __syncthreads();
+    uint32_t *row_hist = hist_g + (u64)r * NBINS;
+    for (uint32_t b = threadIdx.x; b < wd_bins(pass); b += WD_BLOCK) {
+        const uint32_t c = wd_bin_sum(hist, b);
+        if (c) (void)__hip_atomic_fetch_add(row_hist + b, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (threadIdx.x == 0 && (smm[0] | smm[1])) {
+        (void)__hip_atomic_fetch_max(&st->nmn, smm[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        (void)__hip_atomic_fetch_max(&st->mx, smm[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// ---- split form: pick digit `pass` of every row of the group from its
+// histogram, advance its state, clear the histogram and the min / max words.
+// out (null for the top-k): the group's first row of the select's output.
+template <bool F32>
+__global__ __launch_bounds__(WD_BLOCK) void k_wide_pick(uint32_t *__restrict__ hist_g, WideState *__restrict__ st_g,
+                                                        int pass, uint32_t cols, uint32_t k, uint32_t flip,
+                                                        uint32_t *__restrict__ out) {
+    constexpr int PER = NBINS / WD_BLOCK;
+    __shared__ u64 scratch[WD_BLOCK / WAVE + 3];
+    __shared__ uint32_t s_cnt;
+    const uint32_t r = blockIdx.x;
+    WideState *st = st_g + r;
+    const WideState s = *st;
+    if (pass > 0 && s.done) return;  // (workgroup-uniform)
+    uint32_t kk = pass == 0 ? k : s.kk, prefix = pass == 0 ? 0u : s.prefix;
+    const uint32_t cnt_prev = pass == 0 ? cols : s.eqn;
+    uint4 *hq = reinterpret_cast<uint4 *>(hist_g + (u64)r * NBINS + threadIdx.x * PER);
+    u64 hv[PER];
+#pragma unroll
+    for (int q = 0; q < PER / 4; ++q) {
+        const uint4 v = hq[q];
+        hv[4 * q] = v.x, hv[4 * q + 1] = v.y, hv[4 * q + 2] = v.z, hv[4 * q + 3] = v.w;
+        hq[q] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    __syncthreads();  // every thread has read the state before thread 0 rewrites it
+    uint32_t done = 0, answer = 0, eqn = cnt_prev;
+    if (~s.nmn == s.mx) {  // one value fills the bin (or the row)
+        done = 1;
+        answer = s.mx;
+    } else {
+        uint32_t bin = 0;
+        u64 below = 0;
+        (void)block_pick_vals<WD_BLOCK, PER>(hv, (u64)kk, &bin, &below, scratch);
+#pragma unroll
+        for (int j = 0; j < PER; ++j)
+            if (threadIdx.x * PER + j == bin) s_cnt = (uint32_t)hv[j];
+        __syncthreads();
+        eqn = s_cnt;
+        kk -= (uint32_t)below;
+        prefix = pass == 0 ? bin : (prefix << (pass == 1 ? 11 : 10)) | bin;
+        if (pass == 2) {
+            done = 1;
+            answer = prefix;
+        }
+    }
+    if (threadIdx.x == 0) {
+        WideState n;
+        n.kk = kk, n.prefix = prefix, n.done = done, n.answer = answer, n.eqn = eqn, n.nmn = 0u, n.mx = 0u, n.pad = 0u;
+        *st = n;
+        if (done && out) out[r] = WideKey<F32>::bits(answer ^ flip);
+    }
+}
+
+// ---- top-k, split form: (better, equal) of every slice -> cnt_g[row][slice][2]
+template <bool F32, bool VEC>
+__global__ __launch_bounds__(WD_BLOCK, 4) void k_wide_tk_count(const uint32_t *__restrict__ keys, u64 ld, uint32_t cols,
+                                                               uint32_t slice_keys, uint32_t flip,
+                                                               const WideState *__restrict__ st_g,
+                                                               uint32_t *__restrict__ cnt_g) {
+    __shared__ uint32_t sc[2];
+    const uint32_t r = blockIdx.y, s = blockIdx.x;
+    const uint32_t answer = st_g[r].answer;
+    if (threadIdx.x < 2) sc[threadIdx.x] = 0u;
+    __syncthreads();
+    const uint32_t begin = s * slice_keys, end = begin + slice_keys < cols ? begin + slice_keys : cols;
+    const uint32_t *row = keys + (u64)r * ld;
+    uint32_t lt = 0, eq = 0;
+    for (uint32_t base = begin + threadIdx.x * 4u; base < end; base += (uint32_t)(WD_BLOCK * 4 * WD_U)) {
+        uint4 x[WD_U];
+#pragma unroll
+        for (int u = 0; u < WD_U; ++u) x[u] = wd_load4<VEC>(row, base + (uint32_t)(u * WD_BLOCK * 4), end);
+#pragma unroll
+        for (int u = 0; u < WD_U; ++u) {
+            const uint32_t e = base + (uint32_t)(u * WD_BLOCK * 4);
+            const uint32_t w[4] = {x[u].x, x[u].y, x[u].z, x[u].w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t kx = WideKey<F32>::key(w[j]) ^ flip;
+                const bool in = e + (uint32_t)j < end;
+                lt += (in && kx < answer) ? 1u : 0u;
+                eq += (in && kx == answer) ? 1u : 0u;
+            }
+        }
+    }
+    lt = wd_wave_sum(lt);
+    eq = wd_wave_sum(eq);
+    if ((threadIdx.x & (WAVE - 1)) == 0) {
+        (void)__hip_atomic_fetch_add(sc, lt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        (void)__hip_atomic_fetch_add(sc + 1, eq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) cnt_g[((u64)r * gridDim.x + s) * 2u + threadIdx.x] = sc[threadIdx.x];
+}
+
+// Ordered compaction of columns [begin, end): the keys below `answer`, and the
+// first `quota` keys equal to it, go to outputs off, off + 1, ... in column
+// order.  `want` = how many that is (the walk stops there); every store is
+// bounded by k.  wsum: BLOCK / 64 words of LDS.
+template <bool F32, bool VEC, int BLOCK>
+__device__ __forceinline__ void wd_write_range(const uint32_t *__restrict__ row, uint32_t begin, uint32_t end,
+                                               uint32_t flip, uint32_t answer, uint32_t quota, uint32_t off,
+                                               uint32_t want, uint32_t k, uint32_t *__restrict__ vals,
+                                               int32_t *__restrict__ idx, u64 *wsum) {
+    uint32_t lt_run = 0, eq_run = 0;  // workgroup-uniform: kept-so-far counts
+    for (uint32_t cb = begin; cb < end; cb += (uint32_t)(BLOCK * 4)) {
+        if (lt_run + (eq_run < quota ? eq_run : quota) >= want) break;
+        const uint32_t e = cb + threadIdx.x * 4u;
+        const uint4 x = wd_load4<VEC>(row, e, end);
+        const uint32_t w[4] = {x.x, x.y, x.z, x.w};
+        uint32_t kx[4], cl = 0, ce = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            kx[j] = WideKey<F32>::key(w[j]) ^ flip;
+            const bool in = e + (uint32_t)j < end;
+            cl += (in && kx[j] < answer) ? 1u : 0u;
+            ce += (in && kx[j] == answer) ? 1u : 0u;
+        }
+        u64 total;
+        const u64 pre = block_exclusive_scan<BLOCK>((u64)cl | (u64)ce << 32, wsum, &total);
+        uint32_t lt_b = lt_run + (uint32_t)pre, eq_b = eq_run + (uint32_t)(pre >> 32);
+        if (cl | ce) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const bool in = e + (uint32_t)j < end;
+                const bool is_lt = in && kx[j] < answer, is_eq = in && kx[j] == answer;
+                if (is_lt || (is_eq && eq_b < quota)) {
+                    const uint32_t pos = off + lt_b + (eq_b < quota ? eq_b : quota);
+                    if (pos < k) {
+                        if (vals) vals[pos] = WideKey<F32>::bits(kx[j] ^ flip);
+                        if (idx) idx[pos] = (int32_t)(e + (uint32_t)j);
+                    }
+                }
+                lt_b += is_lt ? 1u : 0u;
+                eq_b += is_eq ? 1u : 0u;
+            }
+        }
+        lt_run += (uint32_t)total;
+        eq_run += (uint32_t)(total >> 32);
+    }
+}
+
+// ---- top-k, split form: each slice's offset and quota share from the slices
+// before it, then the ordered compaction of the slice.  vals / idx: the group's
+// first row of the outputs (rows x k), either may be null.
+template <bool F32, bool VEC>
+__global__ __launch_bounds__(WD_BLOCK, 4) void k_wide_tk_write(const uint32_t *__restrict__ keys, u64 ld, uint32_t cols,
+                                                               uint32_t slice_keys, uint32_t flip, uint32_t k,
+                                                               const WideState *__restrict__ st_g,
+                                                               const uint32_t *__restrict__ cnt_g,
+                                                               uint32_t *__restrict__ vals, int32_t *__restrict__ idx) {
+    __shared__ u64 wsum[WD_BLOCK / WAVE];
+    const uint32_t r = blockIdx.y, s = blockIdx.x;
+    const uint32_t answer = st_g[r].answer, kk = st_g[r].kk;
+    const uint32_t *cnt = cnt_g + (u64)r * gridDim.x * 2u;
+    u64 mine = 0;
+    if (threadIdx.x < s) mine = (u64)cnt[2u * threadIdx.x] | (u64)cnt[2u * threadIdx.x + 1u] << 32;
+    u64 before;
+    (void)block_exclusive_scan<WD_BLOCK>(mine, wsum, &before);
+    const uint32_t lt_before = (uint32_t)before, eq_before = (uint32_t)(before >> 32);
+    const uint32_t taken = eq_before < kk ? eq_before : kk, quota = kk - taken;
+    const uint32_t my_lt = cnt[2u * s], my_eq = cnt[2u * s + 1u];
+    const uint32_t want = my_lt + (my_eq < quota ? my_eq : quota);
+    if (want == 0) return;  // (workgroup-uniform) nothing of this slice is kept
+    const uint32_t begin = s * slice_keys, end = begin + slice_keys < cols ? begin + slice_keys : cols;
+    wd_write_range<F32, VEC, WD_BLOCK>(keys + (u64)r * ld, begin, end, flip, answer, quota, lt_before + taken, want, k,
+                                       vals ? vals + (u64)r * k : nullptr, idx ? idx + (u64)r * k : nullptr, wsum);
+}
+
+// ---- fused form: one workgroup per row, every digit in this launch.
+template <bool F32, bool VEC, bool TOPK>
+__global__ __launch_bounds__(WD_FBLOCK, 4) void k_wide_fused(const uint32_t *__restrict__ keys, u64 ld, uint32_t cols,
+                                                             uint32_t k, uint32_t flip, uint32_t *__restrict__ out,
+                                                             uint32_t *__restrict__ vals, int32_t *__restrict__ idx) {
+    constexpr int PER = NBINS / WD_FBLOCK;
+    __shared__ uint32_t hist[WD_COPIES * NBINS];
+    __shared__ uint32_t smm[2];
+    __shared__ u64 scratch[WD_FBLOCK / WAVE + 3];
+    const u64 r = blockIdx.x;
+    const uint32_t *row = keys + r * ld;
+    uint32_t kk = k, prefix = 0, answer = 0;
+    for (int pass = 0; pass < 3; ++pass) {
+        wd_zero_lds<WD_FBLOCK>(hist, smm);
+        __syncthreads();
+        wd_count_range<F32, VEC, WD_FBLOCK>(row, 0u, cols, flip, pass, prefix, hist, smm);
+        __syncthreads();
+        if (~smm[0] == smm[1]) {  // (workgroup-uniform) one value fills the bin: the answer
+            answer = smm[1];
+            break;
+        }
+        u64 hv[PER];
+#pragma unroll
+        for (int j = 0; j < PER; ++j) hv[j] = wd_bin_sum(hist, threadIdx.x * PER + j);
+        uint32_t bin = 0;
+        u64 below = 0;
+        (void)block_pick_vals<WD_FBLOCK, PER>(hv, (u64)kk, &bin, &below, scratch);
+        kk -= (uint32_t)below;
+        prefix = pass == 0 ? bin : (prefix << (pass == 1 ? 11 : 10)) | bin;
+        answer = prefix;
+        __syncthreads();  // the reads of hist and smm before the next digit zeroes them
+    }
+    if (!TOPK) {
+        if (threadIdx.x == 0) out[r] = WideKey<F32>::bits(answer ^ flip);
+        return;
+    }
+    __syncthreads();
+    wd_write_range<F32, VEC, WD_FBLOCK>(row, 0u, cols, flip, answer, kk, 0u, k, k, vals ? vals + r * k : nullptr,
+                                        idx ? idx + r * k : nullptr, scratch);
+}
+
+}  // namespace kth

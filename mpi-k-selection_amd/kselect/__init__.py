@@ -62,6 +62,8 @@ from ._lib import (  # noqa: F401
     KTH_ROWS_MAX_COLS,
     KTH_STATS_WORDS,
     KTH_TOPK_MAX_COLS,
+    KTH_WIDE_MAX_COLS,
+    KTH_WIDE_MAX_SLICES,
     IntVector,
     KthError,
     KthLibraryMissing,
@@ -92,6 +94,16 @@ DEFAULT_SEED = 0x5EED0001
 
 def device_count():
     return LIB.kth_device_count()
+
+
+def wide_rows_plan(rows, cols, num_cu):
+    """(slices, slice_keys, group_rows, scratch_bytes) of the automatic
+    wide-rows plan (kth_wide_rows_plan; host arithmetic, no device needed)."""
+    s, sk, g = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    b = ctypes.c_int64()
+    check(LIB.kth_wide_rows_plan(int(rows), int(cols), int(num_cu), ctypes.byref(s), ctypes.byref(sk), ctypes.byref(g),
+                                 ctypes.byref(b)), "kth_wide_rows_plan")
+    return s.value, sk.value, g.value, b.value
 
 
 def _ptr(x):
@@ -414,6 +426,46 @@ class Selector:
         check(LIB.kth_topk_rows_k16(self._ctx, _ptr(d_keys), int(rows), int(cols), int(k), 1 if largest else 0, kind,
                                     _ptr(d_vals) if d_vals is not None else None,
                                     _ptr(d_idx) if d_idx is not None else None), "kth_topk_rows_k16")
+
+    def rows_wide(self, d_keys, rows, cols, k, d_out, f32=False, ld=None):
+        """Per row of a rows x cols matrix of int32 (f32=True: float32) device
+        keys, cols up to KTH_WIDE_MAX_COLS: the k-th smallest into d_out[r]
+        (kth_select_wide_rows_*; asynchronous on the ctx stream).  ld: elements
+        from one row to the next (default cols)."""
+        if f32:
+            _need_f32(d_keys, "d_keys")
+            _need_f32(d_out, "d_out")
+        fn, what = ((LIB.kth_select_wide_rows_f32, "kth_select_wide_rows_f32") if f32 else
+                    (LIB.kth_select_wide_rows_i32, "kth_select_wide_rows_i32"))
+        check(fn(self._ctx, _ptr(d_keys), int(rows), int(cols), int(cols if ld is None else ld), int(k), _ptr(d_out)),
+              what)
+
+    def topk_rows_wide(self, d_keys, rows, cols, k, d_vals=None, d_idx=None, largest=False, f32=False, ld=None):
+        """Per row of such a matrix: the k smallest (largest=True: largest) keys
+        and their int32 columns, in column order, ties broken by column
+        (kth_topk_wide_rows_*).  d_vals: rows x k of the keys' type, d_idx: rows
+        x k int32; either may be None, not both."""
+        if f32:
+            _need_f32(d_keys, "d_keys")
+            _need_f32(d_vals, "d_vals")
+        dt = getattr(d_idx, "dtype", None)
+        if dt is not None and str(dt).rsplit(".", 1)[-1] != "int32":
+            raise TypeError(f"d_idx must be int32, got {dt}")
+        fn, what = ((LIB.kth_topk_wide_rows_f32, "kth_topk_wide_rows_f32") if f32 else
+                    (LIB.kth_topk_wide_rows_i32, "kth_topk_wide_rows_i32"))
+        check(fn(self._ctx, _ptr(d_keys), int(rows), int(cols), int(cols if ld is None else ld), int(k),
+                 1 if largest else 0, _ptr(d_vals) if d_vals is not None else None,
+                 _ptr(d_idx) if d_idx is not None else None), what)
+
+    def reserve_wide_rows(self, rows, cols):
+        """Pre-size the wide-rows scratch (kth_ctx_reserve_wide_rows): later
+        calls of up to `rows` rows allocate nothing."""
+        check(LIB.kth_ctx_reserve_wide_rows(self._ctx, int(rows), int(cols)), "kth_ctx_reserve_wide_rows")
+
+    def wide_rows_force(self, slices=0, group_rows=0):
+        """Tests and tuning: force this ctx's wide-rows plan; 0 = automatic for
+        that field (kth_ctx_wide_rows_force)."""
+        check(LIB.kth_ctx_wide_rows_force(self._ctx, int(slices), int(group_rows)), "kth_ctx_wide_rows_force")
 
     def topk(self, d_keys, n, k, d_vals=None, d_idx=None, largest=False, f32=False):
         """The k smallest (largest=True: largest) int32 keys of n device keys and

@@ -28,6 +28,8 @@ KTH_DIST_MAX_LEVELS = 3
 KTH_ROWS_MAX_COLS = 16384
 KTH_TOPK_MAX_COLS = 4096
 KTH_ROWS16_MAX_COLS = 8192
+KTH_WIDE_MAX_COLS = 1 << 24
+KTH_WIDE_MAX_SLICES = 256
 KTH_MULTI_MAX_RANKS = 8
 # kth_ctx_test_hook (tests only): fault injectors, off in every new ctx
 KTH_HOOK_FAULT_TOPK_RANK, KTH_HOOK_FAULT_BARRIER, KTH_HOOK_TOPK_SEG_CAP = 1, 2, 3
@@ -136,6 +138,17 @@ PROTOS = {
                                            c_vp]),
     "kth_topk_rows_k16": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int,
                                          ctypes.c_int, c_vp, c_vp]),
+    "kth_select_wide_rows_i32": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
+                                                ctypes.c_int32, c_vp]),
+    "kth_select_wide_rows_f32": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
+                                                ctypes.c_int32, c_vp]),
+    "kth_topk_wide_rows_i32": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
+                                              ctypes.c_int, c_vp, c_vp]),
+    "kth_topk_wide_rows_f32": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
+                                              ctypes.c_int, c_vp, c_vp]),
+    "kth_ctx_reserve_wide_rows": (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int32]),
+    "kth_wide_rows_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i64p]),
+    "kth_ctx_wide_rows_force": (ctypes.c_int, [c_vp, ctypes.c_int32, ctypes.c_int32]),
     "kth_topk_i32": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, c_vp, c_vp]),
     "kth_topk_f32": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, c_vp, c_vp]),
     "kth_topk_k16": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
