@@ -507,6 +507,52 @@ int kth_wide_rows_plan(int64_t rows, int32_t cols, int num_cu, int32_t *slices, 
  * ctx, a negative value, slices > KTH_WIDE_MAX_SLICES. */
 int kth_ctx_wide_rows_force(kth_ctx *ctx, int32_t slices, int32_t group_rows);
 
+/* --- wide rows, 16-bit keys ------------------------------------------------------
+ * The wide-rows calls for int16, uint16, float16 and bfloat16 rows, read as
+ * they are (2 bytes a key; no widened copy): a bfloat16 or float16 logits
+ * matrix of batch x vocabulary.  Row r is the 2-byte words d_keys[r*ld .. r*ld
+ * + cols), ld >= cols in elements.  1 <= k <= cols <= KTH_WIDE_MAX_COLS; rows
+ * >= 0, rows == 0 returns KTH_OK and launches nothing.  kind is KTH_K16_I16 /
+ * U16 / F16 / BF16 and the order is kth_k16_order_key's: -0.0 < +0.0,
+ * subnormals distinct, every NaN equal to every other and above +inf.
+ * Results are exactly those of kth_select_rows_k16 / kth_topk_rows_k16 (for
+ * cols <= KTH_ROWS16_MAX_COLS bit-identical to theirs): a value written has
+ * the bit pattern of an input element, a NaN is written canonical (0x7E00 /
+ * 0x7FC0).  Top-k: the k smallest keys (largest != 0: the k largest) with
+ * their int32 columns, in column order; of the keys equal to the k-th, the
+ * first ones by column; NaNs come last for smallest and first for largest.
+ * d_vals, d_idx: dense rows x k, either may be NULL, not both.  A 16-bit key
+ * has 65536 values and a row can have millions of columns, so the k-th value
+ * nearly always has a large tie group: the tie quota is the normal case here.
+ * Any cols, any ld and any 2-byte aligned base are exact; the fast case is a
+ * 16-byte aligned base with ld % 8 == 0 (16-byte loads of 8 keys, a row's last
+ * partial vector by guarded 2-byte loads), anything else takes guarded 2-byte
+ * loads throughout.  Nothing at or past cols of a row is ever loaded.
+ * Launch behaviour is that of the 32-bit wide-rows calls: asynchronous on the
+ * ctx stream, no host synchronisation, graph-capturable under the conditions
+ * written at kth_select_i32_async.  They use the same ctx scratch (sizes and
+ * the 32 MiB bound unchanged): kth_ctx_reserve_wide_rows(ctx, rows, cols) also
+ * covers these calls and kth_ctx_wide_rows_force also forces their plan.
+ * Every launch sequence leaves that scratch as it found it, so 32-bit and
+ * 16-bit wide calls, and any other call, may alternate on one ctx; no other
+ * ctx buffer nor the last-call word is touched (kth_ctx_last_stats is
+ * unaffected).
+ * KTH_EINVAL before any device work, outputs untouched: a NULL ctx or keys, no
+ * output pointer, rows < 0, a bad cols, ld, k or kind.  KTH_ENODEV without a
+ * GPU.
+ * An order key of 16 bits is two radix digits (11 + 5 bits), not three: the
+ * select reads a row twice, the top-k three times (csrc/kth_rows_wide16.hpp).
+ * kth_wide_rows_plan_k16 is kth_wide_rows_plan for these calls: the same
+ * rule in columns, but that a slice keeps 8192 columns (the same 16 KiB), with
+ * slice_keys a multiple of 8 so that every slice of an aligned row starts on
+ * a 16-byte boundary. */
+int kth_select_wide_rows_k16(kth_ctx *ctx, const void *d_keys, int64_t rows, int32_t cols, int64_t ld,
+                             int32_t k, int kind, uint16_t *d_out);
+int kth_topk_wide_rows_k16(kth_ctx *ctx, const void *d_keys, int64_t rows, int32_t cols, int64_t ld,
+                           int32_t k, int largest, int kind, uint16_t *d_vals, int32_t *d_idx);
+int kth_wide_rows_plan_k16(int64_t rows, int32_t cols, int num_cu, int32_t *slices, int32_t *slice_keys,
+                           int32_t *group_rows, int64_t *scratch_bytes);
+
 /* --- synthetic inputs (bench / tests) --------------------------------------
  * Fills d_out[0..n) with the keys of global indices offset..offset+n of an
  * n_total-key input of family `dist` (oracle/kth_oracle.h enum ko_dist;

@@ -916,19 +916,27 @@ struct WidePlan {
     int64_t scratch_bytes;
 };
 
-WidePlan wide_plan(int64_t rows, int32_t cols, int num_cu, int32_t force_slices, int32_t force_group) {
+// align: a slice's columns are a multiple of it, so that every slice of an
+// aligned row starts on a 16-byte boundary (4 for 4-byte keys, 8 for 2-byte
+// keys).  min_slice: the columns a slice keeps.  The 16-bit calls share every
+// threshold, in columns, but this one: their sweep
+// (profiles/rows_wide16_plan_sweep.jsonl) puts it at 8192 columns, the same
+// 16 KiB (DESIGN.md "16-bit wide rows").
+constexpr int32_t WIDE16_MIN_SLICE = 8192;
+WidePlan wide_plan(int64_t rows, int32_t cols, int num_cu, int32_t force_slices, int32_t force_group,
+                   int32_t align = 4, int32_t min_slice = WIDE_MIN_SLICE) {
     int64_t want = force_slices;
     if (want <= 0) {
         if (rows <= 0 || rows >= (int64_t)WIDE_FUSED_ROWS_PER_CU * num_cu || cols <= WIDE_FUSED_COLS) {
             want = 1;
         } else {
-            want = std::min<int64_t>((int64_t)WIDE_WG_PER_CU * num_cu / rows, cols / WIDE_MIN_SLICE);
+            want = std::min<int64_t>((int64_t)WIDE_WG_PER_CU * num_cu / rows, cols / min_slice);
             if (want < WIDE_MIN_SLICES) want = 1;
         }
     }
     want = std::max<int64_t>(1, std::min<int64_t>(want, KTH_WIDE_MAX_SLICES));
     WidePlan p;
-    p.slice_keys = (int32_t)(((cols + want - 1) / want + 3) & ~(int64_t)3);
+    p.slice_keys = (int32_t)(((cols + want - 1) / want + align - 1) & ~(int64_t)(align - 1));
     p.slices = (cols + p.slice_keys - 1) / p.slice_keys;  // (the last slice is never empty)
     int64_t g = std::min(std::max<int64_t>(rows, 1), p.slices > 1 ? WIDE_GROUP_MAX : WIDE_FUSED_GROUP_MAX);
     if (force_group > 0) g = std::min<int64_t>(g, force_group);
@@ -1008,6 +1016,74 @@ int wide_rows_entry(kth_ctx *c, const void *d_keys, int64_t rows, int32_t cols, 
         KTH_TRY(launch(c, p, gk, g, (uint32_t)cols, (u64)ld, (uint32_t)k, flip, go, gv, gi));
     }
     return KTH_OK;
+}
+
+// 16-bit wide rows (kth_rows_wide16.hpp): the same plan with slices of a
+// multiple of 8 columns, the same scratch, two digits instead of three.
+// CV: k16_ord2's key class (0: uint16, 1: int16, 2: float16 / bfloat16).
+template <int CV, bool VEC, bool TOPK>
+int launch_wide16_group(kth_ctx *c, const WidePlan &p, const uint16_t *keys, int64_t g, uint32_t cols, u64 ld,
+                        uint32_t k, uint32_t flip2, int kind, uint16_t *out, uint16_t *vals, int32_t *idx) {
+    const uint32_t nl2 = kth::k16_nl(kind) * 0x10001u, top2 = kth::k16_top(kind) * 0x10001u;
+    if (p.slices == 1) {
+        kth::k_wide16_fused<CV, VEC, TOPK><<<(int)g, kth::WD_FBLOCK, 0, c->stream>>>(keys, ld, cols, k, flip2, nl2, top2, kind,
+                                                                                  out, vals, idx);
+        return launch_check();
+    }
+    const dim3 grid((unsigned)p.slices, (unsigned)g);
+    const uint32_t sk = (uint32_t)p.slice_keys;
+    uint16_t *sel_out = TOPK ? nullptr : out;
+    kth::k_wide16_count<CV, VEC, 0><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, flip2, nl2, top2,
+                                                                        c->wide_hist.p, c->wide_state.p);
+    kth::k_wide16_pick<<<(int)g, kth::WD_BLOCK, 0, c->stream>>>(c->wide_hist.p, c->wide_state.p, 0, cols, k, flip2, kind,
+                                                             sel_out);
+    kth::k_wide16_count<CV, VEC, 1><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, flip2, nl2, top2,
+                                                                        c->wide_hist.p, c->wide_state.p);
+    kth::k_wide16_pick<<<(int)g, kth::WD_BLOCK, 0, c->stream>>>(c->wide_hist.p, c->wide_state.p, 1, cols, k, flip2, kind,
+                                                             sel_out);
+    if (TOPK) {
+        kth::k_wide16_tk_count<CV, VEC><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, flip2, nl2, top2,
+                                                                            c->wide_state.p, c->wide_cnt.p);
+        kth::k_wide16_tk_write<CV, VEC><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, flip2, nl2, top2, kind, k,
+                                                                            c->wide_state.p, c->wide_cnt.p, vals, idx);
+    }
+    const int rc = launch_check();
+    if (rc != KTH_OK) c->wide_dirty = true;
+    return rc;
+}
+
+template <int CV, bool TOPK>
+int launch_wide16_rows(kth_ctx *c, const WidePlan &p, const uint16_t *keys, int64_t rows, uint32_t cols, u64 ld,
+                       uint32_t k, uint32_t flip2, int kind, uint16_t *out, uint16_t *vals, int32_t *idx) {
+    const bool vec = (reinterpret_cast<uintptr_t>(keys) & 15u) == 0 && ld % 8 == 0;
+    const auto launch = vec ? launch_wide16_group<CV, true, TOPK> : launch_wide16_group<CV, false, TOPK>;
+    for (int64_t r0 = 0; r0 < rows; r0 += p.group_rows) {
+        const int64_t g = std::min<int64_t>(p.group_rows, rows - r0);
+        KTH_TRY(launch(c, p, keys + (u64)r0 * ld, g, cols, ld, k, flip2, kind, out ? out + r0 : nullptr,
+                       vals ? vals + (u64)r0 * k : nullptr, idx ? idx + (u64)r0 * k : nullptr));
+    }
+    return KTH_OK;
+}
+
+// The two 16-bit wide-rows entry points: the argument check, the plan, the
+// scratch and the loop over row groups.
+template <bool TOPK>
+int wide16_rows_entry(kth_ctx *c, const void *d_keys, int64_t rows, int32_t cols, int64_t ld, int32_t k, int kind,
+                      uint16_t *d_out, int largest = 0, uint16_t *d_vals = nullptr, int32_t *d_idx = nullptr) {
+    const bool has_out = TOPK ? d_vals || d_idx : d_out != nullptr;
+    if (!c || !d_keys || !has_out || rows < 0 || cols < 1 || cols > KTH_WIDE_MAX_COLS || ld < cols || k < 1 || k > cols ||
+        kind < KTH_K16_I16 || kind > KTH_K16_BF16)
+        return KTH_EINVAL;
+    if (rows == 0) return KTH_OK;
+    KTH_TRY(set_device(c));
+    const WidePlan p = wide_plan(rows, cols, c->num_cu, c->wide_force_slices, c->wide_force_group, 8, WIDE16_MIN_SLICE);
+    if (p.slices > 1) KTH_TRY(reserve_wide(c, p.group_rows));
+    const uint16_t *keys = static_cast<const uint16_t *>(d_keys);
+    const uint32_t flip2 = TOPK && largest ? 0xFFFFFFFFu : 0u;
+    const uint32_t C = (uint32_t)cols, K = (uint32_t)k;
+    if (kth::k16_float(kind)) return launch_wide16_rows<2, TOPK>(c, p, keys, rows, C, (u64)ld, K, flip2, kind, d_out, d_vals, d_idx);
+    if (kind == KTH_K16_I16) return launch_wide16_rows<1, TOPK>(c, p, keys, rows, C, (u64)ld, K, flip2, kind, d_out, d_vals, d_idx);
+    return launch_wide16_rows<0, TOPK>(c, p, keys, rows, C, (u64)ld, K, flip2, kind, d_out, d_vals, d_idx);
 }
 
 // ------------------------------------------------------- ctx creation, in parts
@@ -2082,6 +2158,27 @@ int kth_ctx_wide_rows_force(kth_ctx *c, int32_t slices, int32_t group_rows) {
     if (!c || slices < 0 || group_rows < 0 || slices > KTH_WIDE_MAX_SLICES) return KTH_EINVAL;
     c->wide_force_slices = slices;
     c->wide_force_group = group_rows;
+    return KTH_OK;
+}
+
+int kth_select_wide_rows_k16(kth_ctx *c, const void *d_keys, int64_t rows, int32_t cols, int64_t ld, int32_t k,
+                             int kind, uint16_t *d_out) {
+    return wide16_rows_entry<false>(c, d_keys, rows, cols, ld, k, kind, d_out);
+}
+
+int kth_topk_wide_rows_k16(kth_ctx *c, const void *d_keys, int64_t rows, int32_t cols, int64_t ld, int32_t k,
+                           int largest, int kind, uint16_t *d_vals, int32_t *d_idx) {
+    return wide16_rows_entry<true>(c, d_keys, rows, cols, ld, k, kind, nullptr, largest, d_vals, d_idx);
+}
+
+int kth_wide_rows_plan_k16(int64_t rows, int32_t cols, int num_cu, int32_t *slices, int32_t *slice_keys,
+                           int32_t *group_rows, int64_t *scratch_bytes) {
+    if (rows < 0 || cols < 1 || cols > KTH_WIDE_MAX_COLS || num_cu < 1) return KTH_EINVAL;
+    const WidePlan p = wide_plan(rows, cols, num_cu, 0, 0, 8, WIDE16_MIN_SLICE);
+    if (slices) *slices = p.slices;
+    if (slice_keys) *slice_keys = p.slice_keys;
+    if (group_rows) *group_rows = p.group_rows;
+    if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
     return KTH_OK;
 }
 

@@ -2090,3 +2090,4 @@ __global__ __launch_bounds__(BLK) void k_state_bcast(const SelState *src, StateP
 #include "kth_k16.hpp"     // (before the 16-bit rows, which use its ord transform)
 #include "kth_rows16.hpp"
 #include "kth_rows_wide.hpp"
+#include "kth_rows_wide16.hpp"

@@ -42,8 +42,10 @@
 // slice starts on a 16-byte boundary and is read with 16-byte loads, the last
 // partial vector of a row by guarded 4-byte loads; otherwise guarded 4-byte
 // loads throughout.  A word becomes an order key right after its load
-// (WideKey: the one place that knows the key type; 16-bit wide rows would add
-// a trait here and leave the passes alone).
+// (WideKey: the one place that knows the key type).  The 16-bit wide rows are
+// kernels of their own (kth_rows_wide16.hpp: two digits of packed 16-bit ords,
+// 8 keys a load); they share the constants, WideState and the wave helpers of
+// this file, and its scratch under the same rule.
 // Included by kth_kernels.hip after kth_rows16.hpp.
 #pragma once
 

@@ -106,6 +106,16 @@ def wide_rows_plan(rows, cols, num_cu):
     return s.value, sk.value, g.value, b.value
 
 
+def wide_rows_plan16(rows, cols, num_cu):
+    """wide_rows_plan for the 16-bit wide-rows calls (kth_wide_rows_plan_k16):
+    slice_keys is a multiple of 8."""
+    s, sk, g = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    b = ctypes.c_int64()
+    check(LIB.kth_wide_rows_plan_k16(int(rows), int(cols), int(num_cu), ctypes.byref(s), ctypes.byref(sk),
+                                     ctypes.byref(g), ctypes.byref(b)), "kth_wide_rows_plan_k16")
+    return s.value, sk.value, g.value, b.value
+
+
 def _ptr(x):
     """Raw address of a torch tensor / numpy array / int."""
     if isinstance(x, int):
@@ -456,6 +466,33 @@ class Selector:
         check(fn(self._ctx, _ptr(d_keys), int(rows), int(cols), int(cols if ld is None else ld), int(k),
                  1 if largest else 0, _ptr(d_vals) if d_vals is not None else None,
                  _ptr(d_idx) if d_idx is not None else None), what)
+
+    def rows_wide16(self, d_keys, rows, cols, k, d_out, kind=None, ld=None):
+        """rows16 for rows of up to KTH_WIDE_MAX_COLS columns: per row of 16-bit
+        device keys the bits of the k-th smallest into the 2-byte element
+        d_out[r] (kth_select_wide_rows_k16; asynchronous on the ctx stream).
+        ld: elements from one row to the next (default cols)."""
+        kind = _k16_kind(d_keys, kind, "d_keys")
+        _k16_same_kind(d_keys, d_out, kind, "d_out")
+        check(LIB.kth_select_wide_rows_k16(self._ctx, _ptr(d_keys), int(rows), int(cols),
+                                           int(cols if ld is None else ld), int(k), kind, _ptr(d_out)),
+              "kth_select_wide_rows_k16")
+
+    def topk_rows_wide16(self, d_keys, rows, cols, k, d_vals=None, d_idx=None, largest=False, kind=None, ld=None):
+        """topk_rows16 for such rows: the k smallest (largest=True: largest) keys
+        and their int32 columns, in column order, ties broken by column
+        (kth_topk_wide_rows_k16).  d_vals: rows x k 2-byte elements of the keys'
+        kind (a NaN canonical), d_idx: rows x k int32; either may be None."""
+        kind = _k16_kind(d_keys, kind, "d_keys")
+        if d_vals is not None:
+            _k16_same_kind(d_keys, d_vals, kind, "d_vals")
+        dt = getattr(d_idx, "dtype", None)
+        if dt is not None and str(dt).rsplit(".", 1)[-1] != "int32":
+            raise TypeError(f"d_idx must be int32, got {dt}")
+        check(LIB.kth_topk_wide_rows_k16(self._ctx, _ptr(d_keys), int(rows), int(cols), int(cols if ld is None else ld),
+                                         int(k), 1 if largest else 0, kind,
+                                         _ptr(d_vals) if d_vals is not None else None,
+                                         _ptr(d_idx) if d_idx is not None else None), "kth_topk_wide_rows_k16")
 
     def reserve_wide_rows(self, rows, cols):
         """Pre-size the wide-rows scratch (kth_ctx_reserve_wide_rows): later

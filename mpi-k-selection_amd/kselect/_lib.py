@@ -149,6 +149,12 @@ PROTOS = {
     "kth_ctx_reserve_wide_rows": (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int32]),
     "kth_wide_rows_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int, c_i32p, c_i32p, c_i32p, c_i64p]),
     "kth_ctx_wide_rows_force": (ctypes.c_int, [c_vp, ctypes.c_int32, ctypes.c_int32]),
+    "kth_select_wide_rows_k16": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
+                                                ctypes.c_int32, ctypes.c_int, c_vp]),
+    "kth_topk_wide_rows_k16": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
+                                              ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
+    "kth_wide_rows_plan_k16": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int, c_i32p, c_i32p, c_i32p,
+                                              c_i64p]),
     "kth_topk_i32": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, c_vp, c_vp]),
     "kth_topk_f32": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, c_vp, c_vp]),
     "kth_topk_k16": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
