@@ -553,6 +553,63 @@ int kth_topk_wide_rows_k16(kth_ctx *ctx, const void *d_keys, int64_t rows, int32
 int kth_wide_rows_plan_k16(int64_t rows, int32_t cols, int num_cu, int32_t *slices, int32_t *slice_keys,
                            int32_t *group_rows, int64_t *scratch_bytes);
 
+/* --- wide rows, ragged: per-row length and per-row k from device memory -----------
+ * The "var" twins of the six wide-rows calls: every row has its own length
+ * and its own rank, read from device arrays when the launches run.  Per-request
+ * top-k sampling (one k a request) and top-k over variable-length score rows
+ * in one padded matrix, in one call, and under graph capture: a captured launch
+ * freezes cols and k, but a replay sees what d_lens and d_ks hold at replay
+ * time.
+ * d_lens, d_ks: device arrays of `rows` int32, 4-byte aligned; either or both
+ * may be NULL.  d_lens == NULL: every row has cols keys.  d_ks == NULL: every
+ * row uses the host k.  They are never read on the host.
+ * cols is the largest row length: the plan, the scratch and the host checks use
+ * it.  Row r is d_keys[r*ld .. r*ld + len_r), len_r = clamp(d_lens[r], 0,
+ * cols).  Nothing at or past len_r of a row is ever loaded.
+ * Top-k: k is the output stride and the bound on every row's k, 1 <= k <=
+ * cols.  k_r = min(clamp(d_ks[r], 0, k), len_r), or min(k, len_r) when d_ks is
+ * NULL.  Entries [0, k_r) of row r's k output slots hold exactly what
+ * kth_topk_wide_rows_* would write for a matrix holding that row's first len_r
+ * columns and rank k_r (column order, ties to the first by column, a NaN
+ * written canonical, `largest` as there).  Entries [k_r, k) are padding: d_idx
+ * -1 and d_vals the zero word (0, +0.0, 0x0000).  Every one of the rows * k
+ * slots of each non-NULL output is written by every call.  d_cnt[r] = k_r;
+ * d_cnt (rows int32, 4-byte aligned) may be NULL.  d_vals and d_idx may each be
+ * NULL, not both.
+ * Select: k_r = clamp(d_ks[r], 1, len_r), or clamp(k, 1, len_r) when d_ks is
+ * NULL: a rank below 1 is the row's minimum, a rank above len_r its maximum.
+ * A row with len_r == 0 writes the zero word.  1 <= k <= cols is checked on
+ * the host either way.
+ * Both arrays NULL: the outputs are bit-identical to the existing call's, and
+ * d_cnt[r] = k.
+ * Everything else is the wide-rows contract: asynchronous on the ctx stream, no
+ * host synchronisation, no allocation after kth_ctx_reserve_wide_rows,
+ * graph-capturable under the conditions written at kth_select_i32_async.  The
+ * same ctx scratch, left as found (row histogram zero, nmn / mx zero), so var
+ * calls, the existing wide calls of either width and any other call may
+ * alternate on one ctx; kth_ctx_last_stats is unaffected;
+ * kth_ctx_wide_rows_force forces their plan too.
+ * KTH_EINVAL before any device work, outputs untouched: a NULL ctx or keys, no
+ * output pointer, rows < 0, a bad cols, ld, k or kind.  rows == 0 returns
+ * KTH_OK and launches nothing.  KTH_ENODEV without a GPU.
+ * (csrc/kth_rows_wide.hpp "Ragged rows": a slice past its row's end and a row
+ * with nothing to select.) */
+int kth_select_wide_rows_var_i32(kth_ctx *ctx, const int32_t *d_keys, int64_t rows, int32_t cols, int64_t ld,
+                                 const int32_t *d_lens, const int32_t *d_ks, int32_t k, int32_t *d_out);
+int kth_select_wide_rows_var_f32(kth_ctx *ctx, const float *d_keys, int64_t rows, int32_t cols, int64_t ld,
+                                 const int32_t *d_lens, const int32_t *d_ks, int32_t k, float *d_out);
+int kth_select_wide_rows_var_k16(kth_ctx *ctx, const void *d_keys, int64_t rows, int32_t cols, int64_t ld,
+                                 const int32_t *d_lens, const int32_t *d_ks, int32_t k, int kind, uint16_t *d_out);
+int kth_topk_wide_rows_var_i32(kth_ctx *ctx, const int32_t *d_keys, int64_t rows, int32_t cols, int64_t ld,
+                               const int32_t *d_lens, const int32_t *d_ks, int32_t k, int largest, int32_t *d_vals,
+                               int32_t *d_idx, int32_t *d_cnt);
+int kth_topk_wide_rows_var_f32(kth_ctx *ctx, const float *d_keys, int64_t rows, int32_t cols, int64_t ld,
+                               const int32_t *d_lens, const int32_t *d_ks, int32_t k, int largest, float *d_vals,
+                               int32_t *d_idx, int32_t *d_cnt);
+int kth_topk_wide_rows_var_k16(kth_ctx *ctx, const void *d_keys, int64_t rows, int32_t cols, int64_t ld,
+                               const int32_t *d_lens, const int32_t *d_ks, int32_t k, int largest, int kind,
+                               uint16_t *d_vals, int32_t *d_idx, int32_t *d_cnt);
+
 /* --- synthetic inputs (bench / tests) --------------------------------------
  * Fills d_out[0..n) with the keys of global indices offset..offset+n of an
  * n_total-key input of family `dist` (oracle/kth_oracle.h enum ko_dist;

@@ -965,22 +965,41 @@ int reserve_wide(kth_ctx *c, int64_t g) {
 
 // One group of g rows: the fused launch, or the split form's sequence -- per
 // digit a count and a pick, for the top-k a count per slice and the compaction.
-template <bool F32, bool VEC, bool TOPK>
+// VAR: the var calls' kernels, which read row r's length and rank from `v`
+// (the group's first row of d_lens / d_ks / d_cnt; `cols` and `k` stay the
+// bounds, and the plan and the scratch are those of the uniform call).
+template <bool F32, bool VEC, bool TOPK, bool VAR>
 int launch_wide_group(kth_ctx *c, const WidePlan &p, const uint32_t *keys, int64_t g, uint32_t cols, u64 ld, uint32_t k,
-                      uint32_t flip, uint32_t *out, uint32_t *vals, int32_t *idx) {
+                      uint32_t flip, uint32_t *out, uint32_t *vals, int32_t *idx, const kth::WideVar &v) {
     if (p.slices == 1) {
-        kth::k_wide_fused<F32, VEC, TOPK><<<(int)g, kth::WD_FBLOCK, 0, c->stream>>>(keys, ld, cols, k, flip, out, vals, idx);
+        if constexpr (VAR)
+            kth::k_wide_fused_var<F32, VEC, TOPK><<<(int)g, kth::WD_FBLOCK, 0, c->stream>>>(keys, ld, cols, k, flip, out,
+                                                                                         vals, idx, v);
+        else
+            kth::k_wide_fused<F32, VEC, TOPK><<<(int)g, kth::WD_FBLOCK, 0, c->stream>>>(keys, ld, cols, k, flip, out, vals, idx);
         return launch_check();
     }
     const dim3 grid((unsigned)p.slices, (unsigned)g);
     const uint32_t sk = (uint32_t)p.slice_keys;
     for (int pass = 0; pass < 3; ++pass) {
-        kth::k_wide_count<F32, VEC><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, flip, pass, c->wide_hist.p,
-                                                                        c->wide_state.p);
-        kth::k_wide_pick<F32><<<(int)g, kth::WD_BLOCK, 0, c->stream>>>(c->wide_hist.p, c->wide_state.p, pass, cols, k, flip,
-                                                                    TOPK ? nullptr : out);
+        if constexpr (VAR) {
+            kth::k_wide_count_var<F32, VEC><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, flip, pass,
+                                                                                c->wide_hist.p, c->wide_state.p, v);
+            kth::k_wide_pick_var<F32><<<(int)g, kth::WD_BLOCK, 0, c->stream>>>(c->wide_hist.p, c->wide_state.p, pass, cols, k,
+                                                                            flip, TOPK ? nullptr : out, v);
+        } else {
+            kth::k_wide_count<F32, VEC><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, flip, pass, c->wide_hist.p,
+                                                                            c->wide_state.p);
+            kth::k_wide_pick<F32><<<(int)g, kth::WD_BLOCK, 0, c->stream>>>(c->wide_hist.p, c->wide_state.p, pass, cols, k, flip,
+                                                                        TOPK ? nullptr : out);
+        }
     }
-    if (TOPK) {
+    if constexpr (TOPK && VAR) {
+        kth::k_wide_tk_count_var<F32, VEC><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, flip, c->wide_state.p,
+                                                                               c->wide_cnt.p, v);
+        kth::k_wide_tk_write_var<F32, VEC><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, flip, k, c->wide_state.p,
+                                                                               c->wide_cnt.p, vals, idx, v);
+    } else if constexpr (TOPK) {
         kth::k_wide_tk_count<F32, VEC><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, flip, c->wide_state.p,
                                                                            c->wide_cnt.p);
         kth::k_wide_tk_write<F32, VEC><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, flip, k, c->wide_state.p,
@@ -991,11 +1010,17 @@ int launch_wide_group(kth_ctx *c, const WidePlan &p, const uint32_t *keys, int64
     return rc;
 }
 
-// The four wide-rows entry points: the argument check, the plan, the scratch
-// and the loop over row groups.
-template <bool F32, bool TOPK>
+// A var call's arrays at row r0 (the host loops advance them like the outputs).
+kth::WideVar wide_var_at(const kth::WideVar &v, int64_t r0) {
+    return kth::WideVar{v.lens ? v.lens + r0 : nullptr, v.ks ? v.ks + r0 : nullptr, v.cnt ? v.cnt + r0 : nullptr};
+}
+
+// The eight 32-bit wide-rows entry points: the argument check, the plan, the
+// scratch and the loop over row groups.
+template <bool F32, bool TOPK, bool VAR = false>
 int wide_rows_entry(kth_ctx *c, const void *d_keys, int64_t rows, int32_t cols, int64_t ld, int32_t k, void *d_out,
-                    int largest = 0, void *d_vals = nullptr, int32_t *d_idx = nullptr) {
+                    int largest = 0, void *d_vals = nullptr, int32_t *d_idx = nullptr,
+                    const kth::WideVar &var = kth::WideVar{}) {
     const bool has_out = TOPK ? d_vals || d_idx : d_out != nullptr;
     if (!c || !d_keys || !has_out || rows < 0 || cols < 1 || cols > KTH_WIDE_MAX_COLS || ld < cols || k < 1 || k > cols)
         return KTH_EINVAL;
@@ -1012,8 +1037,8 @@ int wide_rows_entry(kth_ctx *c, const void *d_keys, int64_t rows, int32_t cols, 
         const uint32_t *gk = keys + (u64)r0 * (u64)ld;
         uint32_t *go = out ? out + r0 : nullptr, *gv = vals ? vals + (u64)r0 * (u64)k : nullptr;
         int32_t *gi = d_idx ? d_idx + (u64)r0 * (u64)k : nullptr;
-        const auto launch = vec ? launch_wide_group<F32, true, TOPK> : launch_wide_group<F32, false, TOPK>;
-        KTH_TRY(launch(c, p, gk, g, (uint32_t)cols, (u64)ld, (uint32_t)k, flip, go, gv, gi));
+        const auto launch = vec ? launch_wide_group<F32, true, TOPK, VAR> : launch_wide_group<F32, false, TOPK, VAR>;
+        KTH_TRY(launch(c, p, gk, g, (uint32_t)cols, (u64)ld, (uint32_t)k, flip, go, gv, gi, wide_var_at(var, r0)));
     }
     return KTH_OK;
 }
@@ -1021,18 +1046,42 @@ int wide_rows_entry(kth_ctx *c, const void *d_keys, int64_t rows, int32_t cols, 
 // 16-bit wide rows (kth_rows_wide16.hpp): the same plan with slices of a
 // multiple of 8 columns, the same scratch, two digits instead of three.
 // CV: k16_ord2's key class (0: uint16, 1: int16, 2: float16 / bfloat16).
-template <int CV, bool VEC, bool TOPK>
+template <int CV, bool VEC, bool TOPK, bool VAR>
 int launch_wide16_group(kth_ctx *c, const WidePlan &p, const uint16_t *keys, int64_t g, uint32_t cols, u64 ld,
-                        uint32_t k, uint32_t flip2, int kind, uint16_t *out, uint16_t *vals, int32_t *idx) {
+                        uint32_t k, uint32_t flip2, int kind, uint16_t *out, uint16_t *vals, int32_t *idx,
+                        const kth::WideVar &v) {
     const uint32_t nl2 = kth::k16_nl(kind) * 0x10001u, top2 = kth::k16_top(kind) * 0x10001u;
     if (p.slices == 1) {
-        kth::k_wide16_fused<CV, VEC, TOPK><<<(int)g, kth::WD_FBLOCK, 0, c->stream>>>(keys, ld, cols, k, flip2, nl2, top2, kind,
-                                                                                  out, vals, idx);
+        if constexpr (VAR)
+            kth::k_wide16_fused_var<CV, VEC, TOPK><<<(int)g, kth::WD_FBLOCK, 0, c->stream>>>(keys, ld, cols, k, flip2, nl2,
+                                                                                          top2, kind, out, vals, idx, v);
+        else
+            kth::k_wide16_fused<CV, VEC, TOPK><<<(int)g, kth::WD_FBLOCK, 0, c->stream>>>(keys, ld, cols, k, flip2, nl2, top2,
+                                                                                      kind, out, vals, idx);
         return launch_check();
     }
     const dim3 grid((unsigned)p.slices, (unsigned)g);
     const uint32_t sk = (uint32_t)p.slice_keys;
     uint16_t *sel_out = TOPK ? nullptr : out;
+    if constexpr (VAR) {
+        kth::k_wide16_count_var<CV, VEC, 0><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, flip2, nl2, top2,
+                                                                                c->wide_hist.p, c->wide_state.p, v);
+        kth::k_wide16_pick_var<<<(int)g, kth::WD_BLOCK, 0, c->stream>>>(c->wide_hist.p, c->wide_state.p, 0, cols, k, flip2,
+                                                                     kind, sel_out, v);
+        kth::k_wide16_count_var<CV, VEC, 1><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, flip2, nl2, top2,
+                                                                                c->wide_hist.p, c->wide_state.p, v);
+        kth::k_wide16_pick_var<<<(int)g, kth::WD_BLOCK, 0, c->stream>>>(c->wide_hist.p, c->wide_state.p, 1, cols, k, flip2,
+                                                                     kind, sel_out, v);
+        if constexpr (TOPK) {
+            kth::k_wide16_tk_count_var<CV, VEC><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, flip2, nl2, top2,
+                                                                                    c->wide_state.p, c->wide_cnt.p, v);
+            kth::k_wide16_tk_write_var<CV, VEC><<<grid, kth::WD_BLOCK, 0, c->stream>>>(
+                keys, ld, cols, sk, flip2, nl2, top2, kind, k, c->wide_state.p, c->wide_cnt.p, vals, idx, v);
+        }
+        const int rc = launch_check();
+        if (rc != KTH_OK) c->wide_dirty = true;
+        return rc;
+    }
     kth::k_wide16_count<CV, VEC, 0><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, flip2, nl2, top2,
                                                                         c->wide_hist.p, c->wide_state.p);
     kth::k_wide16_pick<<<(int)g, kth::WD_BLOCK, 0, c->stream>>>(c->wide_hist.p, c->wide_state.p, 0, cols, k, flip2, kind,
@@ -1052,24 +1101,26 @@ int launch_wide16_group(kth_ctx *c, const WidePlan &p, const uint16_t *keys, int
     return rc;
 }
 
-template <int CV, bool TOPK>
+template <int CV, bool TOPK, bool VAR>
 int launch_wide16_rows(kth_ctx *c, const WidePlan &p, const uint16_t *keys, int64_t rows, uint32_t cols, u64 ld,
-                       uint32_t k, uint32_t flip2, int kind, uint16_t *out, uint16_t *vals, int32_t *idx) {
+                       uint32_t k, uint32_t flip2, int kind, uint16_t *out, uint16_t *vals, int32_t *idx,
+                       const kth::WideVar &var) {
     const bool vec = (reinterpret_cast<uintptr_t>(keys) & 15u) == 0 && ld % 8 == 0;
-    const auto launch = vec ? launch_wide16_group<CV, true, TOPK> : launch_wide16_group<CV, false, TOPK>;
+    const auto launch = vec ? launch_wide16_group<CV, true, TOPK, VAR> : launch_wide16_group<CV, false, TOPK, VAR>;
     for (int64_t r0 = 0; r0 < rows; r0 += p.group_rows) {
         const int64_t g = std::min<int64_t>(p.group_rows, rows - r0);
         KTH_TRY(launch(c, p, keys + (u64)r0 * ld, g, cols, ld, k, flip2, kind, out ? out + r0 : nullptr,
-                       vals ? vals + (u64)r0 * k : nullptr, idx ? idx + (u64)r0 * k : nullptr));
+                       vals ? vals + (u64)r0 * k : nullptr, idx ? idx + (u64)r0 * k : nullptr, wide_var_at(var, r0)));
     }
     return KTH_OK;
 }
 
-// The two 16-bit wide-rows entry points: the argument check, the plan, the
+// The four 16-bit wide-rows entry points: the argument check, the plan, the
 // scratch and the loop over row groups.
-template <bool TOPK>
+template <bool TOPK, bool VAR = false>
 int wide16_rows_entry(kth_ctx *c, const void *d_keys, int64_t rows, int32_t cols, int64_t ld, int32_t k, int kind,
-                      uint16_t *d_out, int largest = 0, uint16_t *d_vals = nullptr, int32_t *d_idx = nullptr) {
+                      uint16_t *d_out, int largest = 0, uint16_t *d_vals = nullptr, int32_t *d_idx = nullptr,
+                      const kth::WideVar &var = kth::WideVar{}) {
     const bool has_out = TOPK ? d_vals || d_idx : d_out != nullptr;
     if (!c || !d_keys || !has_out || rows < 0 || cols < 1 || cols > KTH_WIDE_MAX_COLS || ld < cols || k < 1 || k > cols ||
         kind < KTH_K16_I16 || kind > KTH_K16_BF16)
@@ -1081,9 +1132,11 @@ int wide16_rows_entry(kth_ctx *c, const void *d_keys, int64_t rows, int32_t cols
     const uint16_t *keys = static_cast<const uint16_t *>(d_keys);
     const uint32_t flip2 = TOPK && largest ? 0xFFFFFFFFu : 0u;
     const uint32_t C = (uint32_t)cols, K = (uint32_t)k;
-    if (kth::k16_float(kind)) return launch_wide16_rows<2, TOPK>(c, p, keys, rows, C, (u64)ld, K, flip2, kind, d_out, d_vals, d_idx);
-    if (kind == KTH_K16_I16) return launch_wide16_rows<1, TOPK>(c, p, keys, rows, C, (u64)ld, K, flip2, kind, d_out, d_vals, d_idx);
-    return launch_wide16_rows<0, TOPK>(c, p, keys, rows, C, (u64)ld, K, flip2, kind, d_out, d_vals, d_idx);
+    if (kth::k16_float(kind))
+        return launch_wide16_rows<2, TOPK, VAR>(c, p, keys, rows, C, (u64)ld, K, flip2, kind, d_out, d_vals, d_idx, var);
+    if (kind == KTH_K16_I16)
+        return launch_wide16_rows<1, TOPK, VAR>(c, p, keys, rows, C, (u64)ld, K, flip2, kind, d_out, d_vals, d_idx, var);
+    return launch_wide16_rows<0, TOPK, VAR>(c, p, keys, rows, C, (u64)ld, K, flip2, kind, d_out, d_vals, d_idx, var);
 }
 
 // ------------------------------------------------------- ctx creation, in parts
@@ -2180,6 +2233,45 @@ int kth_wide_rows_plan_k16(int64_t rows, int32_t cols, int num_cu, int32_t *slic
     if (group_rows) *group_rows = p.group_rows;
     if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
     return KTH_OK;
+}
+
+int kth_select_wide_rows_var_i32(kth_ctx *c, const int32_t *d_keys, int64_t rows, int32_t cols, int64_t ld,
+                                 const int32_t *d_lens, const int32_t *d_ks, int32_t k, int32_t *d_out) {
+    return wide_rows_entry<false, false, true>(c, d_keys, rows, cols, ld, k, d_out, 0, nullptr, nullptr,
+                                               kth::WideVar{d_lens, d_ks, nullptr});
+}
+
+int kth_select_wide_rows_var_f32(kth_ctx *c, const float *d_keys, int64_t rows, int32_t cols, int64_t ld,
+                                 const int32_t *d_lens, const int32_t *d_ks, int32_t k, float *d_out) {
+    return wide_rows_entry<true, false, true>(c, d_keys, rows, cols, ld, k, d_out, 0, nullptr, nullptr,
+                                              kth::WideVar{d_lens, d_ks, nullptr});
+}
+
+int kth_select_wide_rows_var_k16(kth_ctx *c, const void *d_keys, int64_t rows, int32_t cols, int64_t ld,
+                                 const int32_t *d_lens, const int32_t *d_ks, int32_t k, int kind, uint16_t *d_out) {
+    return wide16_rows_entry<false, true>(c, d_keys, rows, cols, ld, k, kind, d_out, 0, nullptr, nullptr,
+                                          kth::WideVar{d_lens, d_ks, nullptr});
+}
+
+int kth_topk_wide_rows_var_i32(kth_ctx *c, const int32_t *d_keys, int64_t rows, int32_t cols, int64_t ld,
+                               const int32_t *d_lens, const int32_t *d_ks, int32_t k, int largest, int32_t *d_vals,
+                               int32_t *d_idx, int32_t *d_cnt) {
+    return wide_rows_entry<false, true, true>(c, d_keys, rows, cols, ld, k, nullptr, largest, d_vals, d_idx,
+                                              kth::WideVar{d_lens, d_ks, d_cnt});
+}
+
+int kth_topk_wide_rows_var_f32(kth_ctx *c, const float *d_keys, int64_t rows, int32_t cols, int64_t ld,
+                               const int32_t *d_lens, const int32_t *d_ks, int32_t k, int largest, float *d_vals,
+                               int32_t *d_idx, int32_t *d_cnt) {
+    return wide_rows_entry<true, true, true>(c, d_keys, rows, cols, ld, k, nullptr, largest, d_vals, d_idx,
+                                             kth::WideVar{d_lens, d_ks, d_cnt});
+}
+
+int kth_topk_wide_rows_var_k16(kth_ctx *c, const void *d_keys, int64_t rows, int32_t cols, int64_t ld,
+                               const int32_t *d_lens, const int32_t *d_ks, int32_t k, int largest, int kind,
+                               uint16_t *d_vals, int32_t *d_idx, int32_t *d_cnt) {
+    return wide16_rows_entry<true, true>(c, d_keys, rows, cols, ld, k, kind, nullptr, largest, d_vals, d_idx,
+                                         kth::WideVar{d_lens, d_ks, d_cnt});
 }
 
 }  // extern "C"

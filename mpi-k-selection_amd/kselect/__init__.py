@@ -138,6 +138,17 @@ def _need_f32(x, what):
         raise TypeError(f"{what} must be float32 with f32=True, got {dt}")
 
 
+def _need_i32(x, what):
+    """Anything that carries a dtype (tensor or array) must be int32; None passes."""
+    dt = getattr(x, "dtype", None)
+    if dt is not None and str(dt).rsplit(".", 1)[-1] != "int32":
+        raise TypeError(f"{what} must be int32, got {dt}")
+
+
+def _ptr_or_none(x):
+    return None if x is None else _ptr(x)
+
+
 def _f32_from_bits(bits):
     """np.float32 holding exactly these 32 bits (signed zeros, subnormals and the NaN kept)."""
     return np.array([bits & 0xFFFFFFFF], dtype=np.uint32).view(np.float32)[0]
@@ -493,6 +504,69 @@ class Selector:
                                          int(k), 1 if largest else 0, kind,
                                          _ptr(d_vals) if d_vals is not None else None,
                                          _ptr(d_idx) if d_idx is not None else None), "kth_topk_wide_rows_k16")
+
+    def rows_wide_var(self, d_keys, rows, cols, k, d_out, f32=False, d_lens=None, d_ks=None, ld=None):
+        """rows_wide with a length and a rank per row, read on the device when
+        the launches run (kth_select_wide_rows_var_*): row r is its first
+        clamp(d_lens[r], 0, cols) columns and its rank clamp(d_ks[r], 1, that);
+        an empty row writes the zero word.  d_lens, d_ks: `rows` int32 device
+        elements, None: cols / k for every row."""
+        if f32:
+            _need_f32(d_keys, "d_keys")
+            _need_f32(d_out, "d_out")
+        _need_i32(d_lens, "d_lens")
+        _need_i32(d_ks, "d_ks")
+        fn, what = ((LIB.kth_select_wide_rows_var_f32, "kth_select_wide_rows_var_f32") if f32 else
+                    (LIB.kth_select_wide_rows_var_i32, "kth_select_wide_rows_var_i32"))
+        check(fn(self._ctx, _ptr(d_keys), int(rows), int(cols), int(cols if ld is None else ld), _ptr_or_none(d_lens),
+                 _ptr_or_none(d_ks), int(k), _ptr(d_out)), what)
+
+    def topk_rows_wide_var(self, d_keys, rows, cols, k, d_vals=None, d_idx=None, largest=False, f32=False,
+                           d_lens=None, d_ks=None, d_cnt=None, ld=None):
+        """topk_rows_wide with a length and a k per row, read on the device when
+        the launches run (kth_topk_wide_rows_var_*).  k is the output stride and
+        the bound of every row's k_r = min(clamp(d_ks[r], 0, k), len_r); entries
+        [k_r, k) of a row are written as padding (index -1, the zero word) and
+        d_cnt[r] = k_r.  d_lens, d_ks, d_cnt: `rows` int32 device elements, each
+        may be None."""
+        if f32:
+            _need_f32(d_keys, "d_keys")
+            _need_f32(d_vals, "d_vals")
+        _need_i32(d_idx, "d_idx")
+        _need_i32(d_lens, "d_lens")
+        _need_i32(d_ks, "d_ks")
+        _need_i32(d_cnt, "d_cnt")
+        fn, what = ((LIB.kth_topk_wide_rows_var_f32, "kth_topk_wide_rows_var_f32") if f32 else
+                    (LIB.kth_topk_wide_rows_var_i32, "kth_topk_wide_rows_var_i32"))
+        check(fn(self._ctx, _ptr(d_keys), int(rows), int(cols), int(cols if ld is None else ld), _ptr_or_none(d_lens),
+                 _ptr_or_none(d_ks), int(k), 1 if largest else 0, _ptr_or_none(d_vals), _ptr_or_none(d_idx),
+                 _ptr_or_none(d_cnt)), what)
+
+    def rows_wide16_var(self, d_keys, rows, cols, k, d_out, kind=None, d_lens=None, d_ks=None, ld=None):
+        """rows_wide_var for rows of 16-bit keys (kth_select_wide_rows_var_k16)."""
+        kind = _k16_kind(d_keys, kind, "d_keys")
+        _k16_same_kind(d_keys, d_out, kind, "d_out")
+        _need_i32(d_lens, "d_lens")
+        _need_i32(d_ks, "d_ks")
+        check(LIB.kth_select_wide_rows_var_k16(self._ctx, _ptr(d_keys), int(rows), int(cols),
+                                               int(cols if ld is None else ld), _ptr_or_none(d_lens),
+                                               _ptr_or_none(d_ks), int(k), kind, _ptr(d_out)),
+              "kth_select_wide_rows_var_k16")
+
+    def topk_rows_wide16_var(self, d_keys, rows, cols, k, d_vals=None, d_idx=None, largest=False, kind=None,
+                             d_lens=None, d_ks=None, d_cnt=None, ld=None):
+        """topk_rows_wide_var for rows of 16-bit keys (kth_topk_wide_rows_var_k16)."""
+        kind = _k16_kind(d_keys, kind, "d_keys")
+        if d_vals is not None:
+            _k16_same_kind(d_keys, d_vals, kind, "d_vals")
+        _need_i32(d_idx, "d_idx")
+        _need_i32(d_lens, "d_lens")
+        _need_i32(d_ks, "d_ks")
+        _need_i32(d_cnt, "d_cnt")
+        check(LIB.kth_topk_wide_rows_var_k16(self._ctx, _ptr(d_keys), int(rows), int(cols),
+                                             int(cols if ld is None else ld), _ptr_or_none(d_lens), _ptr_or_none(d_ks),
+                                             int(k), 1 if largest else 0, kind, _ptr_or_none(d_vals),
+                                             _ptr_or_none(d_idx), _ptr_or_none(d_cnt)), "kth_topk_wide_rows_var_k16")
 
     def reserve_wide_rows(self, rows, cols):
         """Pre-size the wide-rows scratch (kth_ctx_reserve_wide_rows): later

@@ -155,6 +155,19 @@ PROTOS = {
                                               ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
     "kth_wide_rows_plan_k16": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int, c_i32p, c_i32p, c_i32p,
                                               c_i64p]),
+    # the var twins: ..., ld, d_lens, d_ks, k, ...; the top-k ones end with d_cnt
+    "kth_select_wide_rows_var_i32": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, c_vp,
+                                                    c_vp, ctypes.c_int32, c_vp]),
+    "kth_select_wide_rows_var_f32": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, c_vp,
+                                                    c_vp, ctypes.c_int32, c_vp]),
+    "kth_select_wide_rows_var_k16": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, c_vp,
+                                                    c_vp, ctypes.c_int32, ctypes.c_int, c_vp]),
+    "kth_topk_wide_rows_var_i32": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, c_vp, c_vp,
+                                                  ctypes.c_int32, ctypes.c_int, c_vp, c_vp, c_vp]),
+    "kth_topk_wide_rows_var_f32": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, c_vp, c_vp,
+                                                  ctypes.c_int32, ctypes.c_int, c_vp, c_vp, c_vp]),
+    "kth_topk_wide_rows_var_k16": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, c_vp, c_vp,
+                                                  ctypes.c_int32, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp]),
     "kth_topk_i32": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, c_vp, c_vp]),
     "kth_topk_f32": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, c_vp, c_vp]),
     "kth_topk_k16": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
