@@ -159,26 +159,14 @@ __global__ __launch_bounds__(DENSE_BLK) void k_head(StepArgs a, CoopArgs x, cons
         }
     };
     bool from_chunks = false;  // block-uniform (kernel arguments and the fresh state)
-#ifdef KTH_HEAD_STORE_SAMPLE  // design exploration: the round-4 head (sample written through)
-    constexpr bool kHeadStore = true;
-#else
-    constexpr bool kHeadStore = false;
-#endif
     if (x.sample_ready)
         hist_sample();
-    else if (gather_head_fast<DENSE_BLK, kHeadStore, F32>(keys, stride, sample, s, lh, plan, blockIdx.x, gridDim.x))
-        from_chunks = !kHeadStore;
+    else if (gather_head_fast<DENSE_BLK, F32>(keys, stride, s, lh, plan, blockIdx.x, gridDim.x))
+        from_chunks = true;
     else
         gather_chunks<DENSE_BLK, true, true, F32>(keys, n_keys, stride, sample, s, lh, plan);
-#ifdef KTH_HEAD_DIAG  // diagnostic build: gather / flush / drain times (slots 4-6 are free on an early window)
-    KTH_STAMP(a, 4);
-#endif
     hist_flush<DENSE_BLK>(lh, plan, x.slots);
     KTH_STAMP(a, 1);
-#ifdef KTH_HEAD_DIAG
-    wait_mem();
-    KTH_STAMP(a, 6);
-#endif
     const EarlyWindow ew{a.r_lo, a.r_hi, x.slack64, x.abs_min};
     bool ok = true;
     for (int L = 0;; ++L) {

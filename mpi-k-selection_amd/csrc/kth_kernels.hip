@@ -23,8 +23,6 @@
 
 namespace kth {
 
-#define KTH_STR2(x) #x
-#define KTH_STR(x) KTH_STR2(x)
 constexpr int BLK = 256;
 #ifndef KTH_MAIN_UNROLL
 #define KTH_MAIN_UNROLL 8
@@ -637,23 +635,18 @@ __device__ __forceinline__ void pick_slot(SelState &ss, const u64 *slot, bool sh
 
 // k_head's gather of the full 1024-key sample chunks: the first digit of a
 // fresh selection has one histogram (both window targets share the empty
-// prefix) and no prefix test, so a key costs a shift and one LDS atomic; the
-// chunk is written through as 16-byte stores (per-key 4-byte atomic stores and
-// bounds tests made the gather ~8 us of VALU issue in 64 CUs).  Chunk c of the
-// sample = keys[c * stride, + SAMPLE_CHUNK); lane l holds 16-byte words l, l+64,
-// l+128, l+192 of it.  Returns false (nothing done) unless every chunk is full
-// and 16-byte aligned; the caller then uses gather_chunks.
-// STORE = false: the chunk's keys only go into the histogram (the sample is
+// prefix) and no prefix test, so a key costs a shift and one LDS atomic (per-key
+// 4-byte atomic stores and bounds tests made the gather ~8 us of VALU issue in
+// 64 CUs).  Chunk c of the sample = keys[c * stride, + SAMPLE_CHUNK); lane l
+// holds 16-byte words l, l+64, l+128, l+192 of it.  Returns false (nothing
+// done) unless every chunk is full and 16-byte aligned; the caller then uses
+// gather_chunks.  The chunk's keys only go into the histogram (the sample is
 // not kept: a later sample level re-reads the chunks from the input).
 // wg / nwg: this workgroup among the nwg that share the chunks.
-#ifndef KTH_HEAD_UNI
-#define KTH_HEAD_UNI 1
-#endif
-constexpr bool HEAD_UNI = KTH_HEAD_UNI != 0;  // the head's one-bin chunks as one atomic (below)
-template <int BLOCK, bool STORE = true, bool F32 = false>
-__device__ __forceinline__ bool gather_head_fast(const int32_t *__restrict__ keys, u64 stride, uint32_t *sample,
-                                                 u64 s, uint32_t (*lh)[NBINS], const HistPlan &plan,
-                                                 uint32_t wg, uint32_t nwg) {
+template <int BLOCK, bool F32 = false>
+__device__ __forceinline__ bool gather_head_fast(const int32_t *__restrict__ keys, u64 stride, u64 s,
+                                                 uint32_t (*lh)[NBINS], const HistPlan &plan, uint32_t wg,
+                                                 uint32_t nwg) {
     static_assert(SAMPLE_CK == 16, "four 16-byte words per lane and chunk");
     // (selects, not plan.x[t]: a runtime index made the plan a private array
     // that the compiler moved into 44 KiB of LDS)
@@ -664,8 +657,6 @@ __device__ __forceinline__ bool gather_head_fast(const int32_t *__restrict__ key
         return false;
     const uint32_t sh = t1 ? plan.shift[1] : plan.shift[0], mask = t1 ? plan.mask[1] : plan.mask[0];
     uint32_t *h = t1 ? lh[1] : lh[0];
-    const __amdgpu_buffer_rsrc_t out =
-        __builtin_amdgcn_make_buffer_rsrc(sample, (short)0, (int)(s * 4), 0x00020000);
     const int lane = threadIdx.x & (WAVE - 1);
     const u64 nchunks = s / SAMPLE_CHUNK;
     const u64 gw = ((u64)wg * BLOCK + threadIdx.x) / WAVE, nw = (u64)nwg * (BLOCK / WAVE);
@@ -681,11 +672,6 @@ __device__ __forceinline__ bool gather_head_fast(const int32_t *__restrict__ key
             q[r].y ^= 0x80000000u;
             q[r].z ^= 0x80000000u;
             q[r].w ^= 0x80000000u;
-            if (STORE) {
-                u32x4 v = {q[r].x, q[r].y, q[r].z, q[r].w};
-                __builtin_amdgcn_raw_buffer_store_b128(v, out, (int)((c * SAMPLE_CHUNK + 4 * (r * WAVE + lane)) * 4),
-                                                       0, 16 /* sc1: written through */);
-            }
         }
         // a chunk whose 1024 keys share one bin (sorted or few-valued input:
         // consecutive keys, one digit) is one atomic, not 1024 serialised on
@@ -697,7 +683,7 @@ __device__ __forceinline__ bool gather_head_fast(const int32_t *__restrict__ key
         for (int r = 0; r < 4; ++r)
             same = same && ((q[r].x >> sh) & mask) == f && ((q[r].y >> sh) & mask) == f &&
                    ((q[r].z >> sh) & mask) == f && ((q[r].w >> sh) & mask) == f;
-        if (HEAD_UNI && __ballot(!same) == 0) {  // wave-uniform
+        if (__ballot(!same) == 0) {  // wave-uniform
             if (lane == 0) atomicAdd(&h[f], (uint32_t)SAMPLE_CHUNK);
             continue;
         }
@@ -750,7 +736,7 @@ __device__ __forceinline__ void head_hist_chunks(const int32_t *__restrict__ key
 #pragma unroll
             for (int j = 0; j < 4; ++j) same = same && code(k4[j], 0) == f0 && code(k4[j], 1) == f1;
         }
-        if (HEAD_UNI && __ballot(!same) == 0) {  // wave-uniform
+        if (__ballot(!same) == 0) {  // wave-uniform
             if (lane == 0) {
                 if (f0 != NONE) atomicAdd(&lh[0][f0], (uint32_t)SAMPLE_CHUNK);
                 if (f1 != NONE) atomicAdd(&lh[1][f1], (uint32_t)SAMPLE_CHUNK);
@@ -851,11 +837,7 @@ struct Stager {
     // One key slot of the wave: `in` = this lane's key is a candidate.
     __device__ __forceinline__ void slot(uint32_t key, bool in, uint32_t row = ~0u) {
         const unsigned long long B = __builtin_amdgcn_ballot_w64(in);
-#ifdef KTH_DIAG_NOSTAGE
-        if (B == 0x123456789ull) {  // diagnostic build only: measures the staging cost
-#else
         if (B) {  // wave-uniform
-#endif
             const uint32_t nb = (uint32_t)__popcll(B);
             if (wfill + nb > CAP) flush();
             const uint32_t below =
@@ -944,7 +926,6 @@ struct OrdStager {
 #pragma unroll
             for (int j = 0; j < FH; ++j) {
                 const uint32_t g = (uint32_t)((h * FH + j) * WAVE + lane), e = 4 * g;
-#ifndef KTH_DIAG_TK5_NOSEGSTORE  // diagnostic builds only (wrong top-k results): cost of the segment stores
                 if (e + 4 <= n4 && e + 4 <= room) {
                     if (seg.nt) {  // wave-uniform
                         typedef uint32_t v4u __attribute__((ext_vector_type(4)));
@@ -964,13 +945,11 @@ struct OrdStager {
                             seg.pos[base + e + q] = (uint8_t)(pv[j] >> (8 * q));
                         }
                 }
-#endif
                 nc += (is_cand(kv[j].x, e) ? 1u : 0u) + (is_cand(kv[j].y, e + 1) ? 1u : 0u) +
                       (is_cand(kv[j].z, e + 2) ? 1u : 0u) + (is_cand(kv[j].w, e + 3) ? 1u : 0u);
             }
         }
         if (seg_fill + nw > seg.cap && lane == 0) *seg.ovf = 1u;
-#ifndef KTH_DIAG_TK5_NOCANDS  // diagnostic builds only (wrong results): cost of the candidate filter
         // pass 2: one reservation for the wave, each lane its candidates from its offset
         const uint32_t incl = wave_incl_scan32(nc);
         const uint32_t nin = (uint32_t)__builtin_amdgcn_readlane((int)incl, WAVE - 1);
@@ -999,7 +978,6 @@ struct OrdStager {
             }
             winside += nin;
         }
-#endif
         // the 0-3 entries not written move to the front (read before any write: one wave, in order)
         const uint32_t left = wfill - nw;
         uint32_t kx = 0;
@@ -1046,9 +1024,6 @@ struct OrdStager {
         }
         const uint32_t n0 = (uint32_t)__popcll(b0), n1 = (uint32_t)__popcll(b1), n2 = (uint32_t)__popcll(b2);
         const uint32_t total = n0 + n1 + n2 + (uint32_t)__popcll(b3);
-#ifdef KTH_DIAG_TK5_NOSTAGE  // diagnostic builds only (wrong top-k results): cost of the staging
-        return total;
-#endif
         if (wfill + total > CAP) flush();
         uint8_t *pb = reinterpret_cast<uint8_t *>(reg + CAP);
         auto at = [](unsigned long long b, uint32_t base) {
@@ -1167,11 +1142,7 @@ __global__ __launch_bounds__(BLK) void k_main(StepArgs a, uint32_t *__restrict__
                                               uint32_t *__restrict__ tflags, uint32_t *__restrict__ cand_rows,
                                               TkSeg seg) {
     constexpr int U = MAIN_UNROLL, S = MAIN_SUB, K = 4 * S;
-#ifdef KTH_DIAG_NOROWS  // diagnostic builds only (wrong top-k results): cost of the row tags
-    constexpr bool ROWS = false;
-#else
     constexpr bool ROWS = TF == 3 || TF == 4;
-#endif
     constexpr bool ORD = TF >= 5;  // index-ordered staging of the kept side (OrdStager)
     static_assert(!(F32 && ORD), "the staged top-k is int32 only: its segments hold the caller's words");
     static_assert(U % S == 0, "MAIN_UNROLL is a multiple of MAIN_SUB");
@@ -1205,15 +1176,10 @@ __global__ __launch_bounds__(BLK) void k_main(StepArgs a, uint32_t *__restrict__
         // at a tile's start stream faster here, not more.  Plain loads instead
         // of nontemporal ones: select 0.676 -> 0.762 ms, top-k k = 2^24 / 2^27
         // 1.003 / 2.015 -> 1.082 / 2.126 ms (one box, round 5).
-#ifndef KTH_MAIN_FIRST  // design exploration: loads before the wait, and the wait's vmcnt
-#define KTH_MAIN_FIRST 1
-#define KTH_MAIN_WAITN 0
-#endif
+        x[0] = load_nt(src);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
-        for (int u = 0; u < KTH_MAIN_FIRST; ++u) x[u] = load_nt(src + u * BLK);
-        asm volatile("s_waitcnt vmcnt(" KTH_STR(KTH_MAIN_WAITN) ")" ::: "memory");
-#pragma unroll
-        for (int u = KTH_MAIN_FIRST; u < U; ++u) x[u] = load_nt(src + u * BLK);
+        for (int u = 1; u < U; ++u) x[u] = load_nt(src + u * BLK);
     };
     // (Issuing the first tile's loads before the advance made the pass slower,
     // 656 vs 642 us: the advance's histogram loads then wait behind them.)
@@ -1237,10 +1203,6 @@ __global__ __launch_bounds__(BLK) void k_main(StepArgs a, uint32_t *__restrict__
     // TF 5 / 6: the counts of one wave-row slot's 4 keys (as scan_keys) and
     // their ordered staging (full tiles only)
     auto ord_keys = [&](const uint4 &q) -> uint32_t {
-#ifdef KTH_DIAG_TK5_NOROW  // diagnostic builds only (wrong results): the pass without the staging compares
-        clt += q.x < (uint32_t)slo;
-        return 0u;
-#endif
         clt += ((int32_t)q.x < slo ? 1u : 0u) + ((int32_t)q.y < slo ? 1u : 0u) + ((int32_t)q.z < slo ? 1u : 0u) +
                ((int32_t)q.w < slo ? 1u : 0u);
         return os.template row<TF>(q, (uint32_t)lane, ceqlo, ceqhi);  // (the edges are counted there)
@@ -1309,11 +1271,7 @@ __global__ __launch_bounds__(BLK) void k_main(StepArgs a, uint32_t *__restrict__
             // byte tiles_done % 4 of lane (tiles_done / 4) % 64 (stored every 256 tiles)
             facc = (uint32_t)lane == (tiles_done / 4) % WAVE ? facc | rows << (8 * (tiles_done % 4)) : facc;
         }
-#ifdef KTH_DIAG_NOROWW  // diagnostic builds only (wrong top-k results): cost of the row words
-        if constexpr (TF >= 5) {
-#else
         if constexpr (TF >= 3) {
-#endif
             static_assert(U == 8, "k_main<3/4> packs four rows' counts into each of two words");
             // #beyond per row: a lane holds <= 4 keys of a row, so rows 0-3 / 4-7
             // fit 8-bit fields of b0 / b1 over a 32-lane half (<= 128); two DPP
@@ -1338,10 +1296,8 @@ __global__ __launch_bounds__(BLK) void k_main(StepArgs a, uint32_t *__restrict__
                 c += dpp_add<0x142, 0xA>(c);  // row_bcast:15 -> lanes 31, 63: the halves' sums
                 return c;
             };
-#ifndef KTH_DIAG_NOSCAN  // diagnostic builds only (wrong top-k results)
             b0 = half_scan(b0);
             b1 = half_scan(b1);
-#endif
             uint32_t *rx = rowx[wid];
             if ((lane & 31) == 31) {
                 rx[lane >> 5] = b0;
@@ -1399,13 +1355,11 @@ __global__ __launch_bounds__(BLK) void k_main(StepArgs a, uint32_t *__restrict__
 #pragma unroll
             for (int q = 0; q < RW_REGS; ++q) grp[q] = mine && gi == (uint32_t)q ? v : grp[q];
             ++tiles_done;
-#ifndef KTH_DIAG_NOPEND  // diagnostic builds only (wrong top-k results): cost of the row-word stores
             if (tiles_done % (RW_REGS * TK5_WIN_TILES) == 0) {  // wave-uniform: 128 tiles' words
 #pragma unroll
                 for (int q = 0; q < RW_REGS; ++q)
                     wseg[(tiles_done - RW_REGS * TK5_WIN_TILES) * U + q * WAVE + lane] = grp[q];
             }
-#endif
             // TF 5 / 6: the entries staged before each window (lane w % 64 of
             // wsr), so the staged top-k kernels take the windows independently
             if constexpr (ORD)
@@ -1522,7 +1476,7 @@ __global__ __launch_bounds__(BLK) void k_main(StepArgs a, uint32_t *__restrict__
                         // a workgroup's candidates are a run of values) add once
                         const uint32_t b = (region[q][i] - base) >> sh, f = __builtin_amdgcn_readfirstlane(b);
                         const u64 act = __ballot(true);
-                        if (HEAD_UNI && __ballot(b != f) == 0) {
+                        if (__ballot(b != f) == 0) {
                             if ((uint32_t)lane == (uint32_t)__builtin_ctzll(act)) atomicAdd(&phist[f], (uint32_t)__popcll(act));
                         } else {
                             atomicAdd(&phist[b], 1u);

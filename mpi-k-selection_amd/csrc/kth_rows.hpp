@@ -21,17 +21,6 @@
 namespace kth {
 
 constexpr int RW_BLOCK = 256;
-#ifndef KTH_TOPK_RELOAD
-#define KTH_TOPK_RELOAD 1
-#endif
-constexpr bool TOPK_RELOAD = KTH_TOPK_RELOAD;  // top-k compaction re-reads full rows from L2
-#ifndef KTH_TOPK_KEYS_COMPACT
-#define KTH_TOPK_KEYS_COMPACT 1
-#endif
-constexpr bool TOPK_KEYS_COMPACT = KTH_TOPK_KEYS_COMPACT;  // unstaged full top-k rows compact from key[]
-#ifndef KTH_TOPK_NT
-#define KTH_TOPK_NT 1  // top-k rows load with the non-temporal hint too (the staged path reads a row once)
-#endif
 #ifndef KTH_ROWS_WAVES
 #define KTH_ROWS_WAVES 4  // waves per SIMD the register budget is held to (<= 128 VGPRs)
 #endif
@@ -146,7 +135,7 @@ __device__ __forceinline__ uint32_t opaque(uint32_t x) {
 }
 __device__ __forceinline__ float opaque(float x) { return __uint_as_float(opaque(__float_as_uint(x))); }
 
-// The first kernel's selection (A/B reference, KTH_ROWS_LEGACY): four 8-bit
+// The plain radix selection, which row_select_range falls back to: four 8-bit
 // radix digits of the raw order key, the first counted into R0 copies.
 // Returns the kk-th smallest of the lane keys; kk becomes its rank among the
 // keys equal to it.
@@ -770,16 +759,10 @@ __device__ __forceinline__ uint32_t row_select_fast(uint32_t (&key)[KPL], uint32
                 __builtin_amdgcn_sched_barrier(0);  // keep the groups apart: no hoisting across them (VGPRs)
             }
         };
-#ifndef KTH_DIAG_ROWS_NOSTAGE  // (timing diagnostics only: wrong results)
         if (F32 && vmap)
             stage_rows(std::true_type{});
         else
             stage_rows(std::false_type{});
-#endif
-#ifdef KTH_DIAG_ROWS_NOTAIL
-        *topk_done = true;
-        return staged;
-#endif
         __builtin_amdgcn_wave_barrier();
         // the list: the staged keys of bin B (a handful of rounds over <= nc pairs)
         for (uint32_t i0 = 0; i0 < staged; i0 += WAVE) {  // wave-uniform
@@ -850,14 +833,10 @@ __device__ __forceinline__ uint32_t row_select_fast(uint32_t (&key)[KPL], uint32
             const bool keep = lt2 || (eq2 && rank < kk);
             const unsigned long long bk = __ballot(keep);
             const uint32_t pos = out + __builtin_amdgcn_mbcnt_hi((uint32_t)(bk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bk, 0u));
-#ifndef KTH_DIAG_ROWS_NOSTORE  // (timing diagnostics only: no output)
             if (keep) {
                 if (tko->vals) tko->vals[tko->obase + pos] = (F32 && vmap) ? pr.x : raw_of_key<F32>(pr.x ^ flip);
                 if (tko->idx) tko->idx[tko->obase + pos] = (int32_t)pr.y;
             }
-#else
-            asm volatile("" ::"v"(pos), "v"(pr.x), "v"(pr.y), "v"((uint32_t)keep));
-#endif
             out += (uint32_t)__popcll(bk);
             eq_seen += (uint32_t)__popcll(be);
         }
@@ -876,7 +855,7 @@ __device__ __forceinline__ uint32_t row_select_fast(uint32_t (&key)[KPL], uint32
 // order reversed: ~key).
 // FULL: cols == 64 * KPL and 16-byte aligned rows (unguarded loads, row_select_fast).
 template <bool F32, int KPL, bool VEC, int R0, bool TOPK, bool FULL>
-__global__ __launch_bounds__(RW_BLOCK, !VEC ? 1 : (TOPK && !(TOPK_RELOAD && FULL)) ? 2 : TOPK ? KTH_TOPK_ROWS_WAVES : KTH_ROWS_WAVES) void k_rows_reg(const uint32_t *__restrict__ m, u64 rows, uint32_t cols,
+__global__ __launch_bounds__(RW_BLOCK, !VEC ? 1 : (TOPK && !FULL) ? 2 : TOPK ? KTH_TOPK_ROWS_WAVES : KTH_ROWS_WAVES) void k_rows_reg(const uint32_t *__restrict__ m, u64 rows, uint32_t cols,
                                                       uint32_t k, uint32_t *__restrict__ out, uint32_t flip,
                                                       uint32_t *__restrict__ vals, int32_t *__restrict__ idx) {
     static_assert(KPL % 4 == 0, "16-byte loads");
@@ -898,7 +877,7 @@ __global__ __launch_bounds__(RW_BLOCK, !VEC ? 1 : (TOPK && !(TOPK_RELOAD && FULL
                 // (top-k rows whose bins cannot be staged re-read the row; with
                 // the non-temporal hint that re-read comes from HBM, not L2 -- rare)
                 const uint4 *src = reinterpret_cast<const uint4 *>(row + (j * WAVE + lane) * 4);
-                const uint4 x = TOPK && !KTH_TOPK_NT ? *src : load_nt(src);
+                const uint4 x = load_nt(src);
                 key[4 * j + 0] = x.x;
                 key[4 * j + 1] = x.y;
                 key[4 * j + 2] = x.z;
@@ -913,21 +892,9 @@ __global__ __launch_bounds__(RW_BLOCK, !VEC ? 1 : (TOPK && !(TOPK_RELOAD && FULL
                     if (TOPK) asm volatile("" : "+v"(key[j]));
                 }
             }
-#ifdef KTH_ROWS_LEGACY
-            if (F32) {
-#pragma unroll
-                for (int j = 0; j < KPL; ++j) key[j] = key_of_f32(key[j]) ^ flip;
-            }
-            answer = row_select_radix<KPL, R0>(key, hist, lane, kk);
-#else
-#ifndef KTH_DIAG_ROWS_SMALLOUT
             const TopkOut tko{k, vals, idx, r * (u64)k};
-#else  // (timing only: every row's output to one of 64 row slots, L2-resident)
-            const TopkOut tko{k, vals, idx, (r & 63) * (u64)k};
-#endif
             answer = row_select_fast<F32, KPL, R0, TOPK, TOPK>(key, hist, lane, kk, TOPK ? flip : 0u,
                                                                 TOPK ? &eqn : nullptr, &tko, &topk_done);
-#endif
         } else {
 #pragma unroll
         for (int j = 0; j < KPL / 4; ++j) {
@@ -946,18 +913,10 @@ __global__ __launch_bounds__(RW_BLOCK, !VEC ? 1 : (TOPK && !(TOPK_RELOAD && FULL
             for (int q = 0; q < 4; ++q)
                 key[4 * j + q] = e + q < cols ? ((F32 ? key_of_f32(v[q]) : key_of_i32(v[q])) ^ flip) : 0xFFFFFFFFu;
         }
-#ifdef KTH_ROWS_LEGACY
-        answer = row_select_radix<KPL, R0>(key, hist, lane, kk);
-#else
         answer = row_select_range<F32, KPL, R0>(key, hist, lane, kk, cols, flip);
-#endif
         }
         if (!TOPK) {
-#ifndef KTH_DIAG_ROWS_NOOUT
             if (lane == 0) out[r] = raw_of_key<F32>(answer ^ flip);
-#else
-            asm volatile("" ::"v"(answer));
-#endif
         } else if (!topk_done) {
             // Compaction in column order.  Group j holds columns (64*j + lane)*4 + q:
             // lane-major, then q.  For each q a ballot of the selected keys and
@@ -1044,7 +1003,7 @@ __global__ __launch_bounds__(RW_BLOCK, !VEC ? 1 : (TOPK && !(TOPK_RELOAD && FULL
                 }
             };
             const bool all_ties = FULL && kk == eqn;
-            if (TOPK_KEYS_COMPACT && !F32 && TOPK_RELOAD && FULL) {
+            if (!F32 && FULL) {
                 // int rows: key[] still holds the row's order keys (KEYS_OUT):
                 // compact from the registers -- the re-read below comes from HBM
                 // (the row was loaded non-temporal), a second pass over the
@@ -1056,7 +1015,7 @@ __global__ __launch_bounds__(RW_BLOCK, !VEC ? 1 : (TOPK && !(TOPK_RELOAD && FULL
                     group((uint32_t)(j * WAVE + lane) * 4u, g);
                     __builtin_amdgcn_sched_barrier(0);  // keep the groups apart: no hoisting across them (VGPRs)
                 }
-            } else if (TOPK_RELOAD && FULL && all_ties) {
+            } else if (FULL && all_ties) {
                 // the row again, from L2, every group's load in flight at once (the
                 // keys' registers are free by now): one round trip per row, not
                 // one per two groups
@@ -1077,7 +1036,7 @@ __global__ __launch_bounds__(RW_BLOCK, !VEC ? 1 : (TOPK && !(TOPK_RELOAD && FULL
                     group_all(e0 + (uint32_t)(j * WAVE * 4), g);
                     __builtin_amdgcn_sched_barrier(0);  // keep the groups apart: no hoisting across them (VGPRs)
                 }
-            } else if (TOPK_RELOAD && FULL) {
+            } else if (FULL) {
                 // FULL rows re-read their keys here (from L2: loaded without the
                 // non-temporal hint), two groups ahead, in a rolled loop, instead of
                 // keeping all KPL keys live through the compaction: 4 waves per

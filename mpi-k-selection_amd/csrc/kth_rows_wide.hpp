@@ -24,12 +24,9 @@
 //
 // The first digit of a float row is sign + exponent + two mantissa bits: a
 // randn row puts most keys into about ten bins, and a wave's LDS adds to one
-// address serialise.  The remedy of k_rows_reg and the 16-bit rows, WD_COPIES
-// histogram copies with lane % WD_COPIES picking one (exact for any input, the
-// copies summed at the flush / pick), was measured here and lost: 2 and 4
-// copies gain nothing on randn rows in either form and cost a split-form
-// workgroup its larger clear and flush (DESIGN.md "Wide rows").  One copy is
-// the default; KTH_WIDE_COPIES rebuilds the others.
+// address serialise.  The remedy of k_rows_reg and the 16-bit rows, several
+// histogram copies with the lane picking one, was measured here and lost
+// (DESIGN.md "Wide rows"): a workgroup keeps one LDS histogram.
 //
 // Top-k: the select leaves the k-th key and the tie quota (k minus the keys
 // strictly better).  Split: k_wide_tk_count writes (better, equal) per slice,
@@ -51,11 +48,6 @@
 
 namespace kth {
 
-#ifndef KTH_WIDE_COPIES
-#define KTH_WIDE_COPIES 1  // LDS histogram copies per workgroup (a power of two)
-#endif
-constexpr int WD_COPIES = KTH_WIDE_COPIES;
-static_assert((WD_COPIES & (WD_COPIES - 1)) == 0, "lane % WD_COPIES is a mask");
 constexpr int WD_BLOCK = 256;    // split-form kernels
 constexpr int WD_FBLOCK = 512;   // fused kernel: one workgroup per row
 constexpr int WD_U = 4;          // 16-byte loads in flight per thread in the counting passes
@@ -167,13 +159,12 @@ __device__ __forceinline__ uint32_t wd_wave_sum(uint32_t x) {
 }
 
 // Digit `pass` of the keys of columns [begin, end) that match `prefix`, counted
-// into the workgroup's LDS copies `hist`; smm[0 .. 1] take max(~key), max(key)
+// into the workgroup's LDS histogram `hist`; smm[0 .. 1] take max(~key), max(key)
 // of those keys.  The caller zeroes hist and smm before and synchronises after.
 template <bool F32, bool VEC, int BLOCK>
 __device__ __forceinline__ void wd_count_range(const uint32_t *__restrict__ row, uint32_t begin, uint32_t end,
                                                uint32_t flip, int pass, uint32_t prefix, uint32_t *hist,
                                                uint32_t *smm) {
-    uint32_t *mine = hist + (threadIdx.x & (WD_COPIES - 1)) * NBINS;
     const uint32_t mshift = pass == 1 ? 21u : 10u, dshift = wd_shift(pass), dmask = wd_bins(pass) - 1u;
     uint32_t nmn = 0, mx = 0;
     for (uint32_t base = begin + threadIdx.x * 4u; base < end; base += (uint32_t)(BLOCK * 4 * WD_U)) {
@@ -188,7 +179,7 @@ __device__ __forceinline__ void wd_count_range(const uint32_t *__restrict__ row,
             for (int j = 0; j < 4; ++j) {
                 const uint32_t kx = WideKey<F32>::key(w[j]) ^ flip;
                 if (e + (uint32_t)j < end && (pass == 0 || (kx >> mshift) == prefix)) {
-                    wd_add(mine, (kx >> dshift) & dmask);
+                    wd_add(hist, (kx >> dshift) & dmask);
                     nmn = ~kx > nmn ? ~kx : nmn;
                     mx = kx > mx ? kx : mx;
                 }
@@ -205,14 +196,8 @@ __device__ __forceinline__ void wd_count_range(const uint32_t *__restrict__ row,
 
 template <int BLOCK>
 __device__ __forceinline__ void wd_zero_lds(uint32_t *hist, uint32_t *smm) {
-    for (int i = threadIdx.x; i < WD_COPIES * NBINS; i += BLOCK) hist[i] = 0u;
+    for (int i = threadIdx.x; i < NBINS; i += BLOCK) hist[i] = 0u;
     if (threadIdx.x < 2) smm[threadIdx.x] = 0u;
-}
-__device__ __forceinline__ uint32_t wd_bin_sum(const uint32_t *hist, uint32_t bin) {
-    uint32_t s = 0;
-#pragma unroll
-    for (int c = 0; c < WD_COPIES; ++c) s += hist[c * NBINS + bin];
-    return s;
 }
 
 // Ordered compaction of columns [begin, end): the keys below `answer`, and the

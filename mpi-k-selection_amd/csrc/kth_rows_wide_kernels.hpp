@@ -25,7 +25,7 @@ __global__ __launch_bounds__(WD_BLOCK, 4) void WD_K(k_wide_count)(const uint32_t
                                                                   uint32_t cols, uint32_t slice_keys, uint32_t flip,
                                                                   int pass, uint32_t *__restrict__ hist_g,
                                                                   WideState *__restrict__ st_g WD_VAR_PARAM) {
-    __shared__ uint32_t hist[WD_COPIES * NBINS];
+    __shared__ uint32_t hist[NBINS];
     __shared__ uint32_t smm[2];
     const uint32_t r = blockIdx.y, s = blockIdx.x;
     WideState *st = st_g + r;
@@ -43,7 +43,7 @@ __global__ __launch_bounds__(WD_BLOCK, 4) void WD_K(k_wide_count)(const uint32_t
     __syncthreads();
     uint32_t *row_hist = hist_g + (u64)r * NBINS;
     for (uint32_t b = threadIdx.x; b < wd_bins(pass); b += WD_BLOCK) {
-        const uint32_t c = wd_bin_sum(hist, b);
+        const uint32_t c = hist[b];
         if (c) (void)__hip_atomic_fetch_add(row_hist + b, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     if (threadIdx.x == 0 && (smm[0] | smm[1])) {
@@ -198,7 +198,7 @@ __global__ __launch_bounds__(WD_FBLOCK, 4) void WD_K(k_wide_fused)(const uint32_
                                                                    uint32_t *__restrict__ vals,
                                                                    int32_t *__restrict__ idx WD_VAR_PARAM) {
     constexpr int PER = NBINS / WD_FBLOCK;
-    __shared__ uint32_t hist[WD_COPIES * NBINS];
+    __shared__ uint32_t hist[NBINS];
     __shared__ uint32_t smm[2];
     __shared__ u64 scratch[WD_FBLOCK / WAVE + 3];
     const u64 r = blockIdx.x;
@@ -223,7 +223,7 @@ __global__ __launch_bounds__(WD_FBLOCK, 4) void WD_K(k_wide_fused)(const uint32_
         }
         u64 hv[PER];
 #pragma unroll
-        for (int j = 0; j < PER; ++j) hv[j] = wd_bin_sum(hist, threadIdx.x * PER + j);
+        for (int j = 0; j < PER; ++j) hv[j] = hist[threadIdx.x * PER + j];
         uint32_t bin = 0;
         u64 below = 0;
         (void)block_pick_vals<WD_FBLOCK, PER>(hv, (u64)kk, &bin, &below, scratch);
