@@ -617,6 +617,93 @@ int kth_topk_wide_rows_var_k16(kth_ctx *ctx, const void *d_keys, int64_t rows, i
 int kth_fill_synthetic(kth_ctx *ctx, int32_t *d_out, int64_t n, int64_t offset, int64_t n_total,
                        int dist, uint64_t seed, int32_t param);
 
+/* --- wide rows, top-p: the nucleus of each row of float logits -----------------
+ * The filter of an LLM sampler that the var top-k leaves open: keep the
+ * smallest set of the largest logits of a row whose softmax mass reaches p.
+ * A nucleus is a weighted select -- the value at which the probability mass of
+ * the larger keys reaches p, where a select looks for the count reaching k --
+ * and is found by the wide rows' radix passes with a mass per bin, not by
+ * sorting the row.  float32 rows (_f32) and float16 / bfloat16 rows (_k16,
+ * kind KTH_K16_F16 or KTH_K16_BF16; the integer kinds are KTH_EINVAL).
+ *
+ * Per-row arrays and scalars.  d_lens is what it is in the var calls: len_r =
+ * clamp(d_lens[r], 0, cols), NULL: cols; nothing at or past len_r of a row is
+ * ever loaded.  d_ps, d_temps: device arrays of `rows` float32, 4-byte
+ * aligned, read only on the device when the launches run; either may be NULL,
+ * then the host scalar p / temp holds for every row.  temp must be finite and
+ * > 0 (checked on the host either way); a device temps[r] that is not finite
+ * or is <= 0 counts as 1.0.
+ *
+ * The row.  Order the row's first len_r keys by the library's float order,
+ * largest first, ties by column -- the order of the var top-k with largest =
+ * 1, which puts NaN on top.  Let m be the first key.
+ * Weights.  w_i = 1 for a key equal to m in that order; w_i = 0 if m is +inf
+ * or NaN, or if x_i is -inf; otherwise w_i = exp((x_i - m) / T_r).  S(j) = the
+ * weight of the first j keys, Z = S(len_r).
+ * The nucleus size n_r.  For 0 <= p_r < 1 the contract value is the least n >=
+ * 1 with S(n) >= p_r * Z.  p_r < 0 counts as 0 (greedy: n_r = 1).  p_r >= 1 or
+ * NaN: n_r = len_r exactly, no filter.  len_r == 0: n_r = 0.
+ *
+ * Tolerance.  The device evaluates a weight in float32 and sums weights as
+ * 64-bit fixed point, rint(w * 2^39).  A call may therefore return any n
+ * inside a band around the contract value:
+ *     S(n) >= p * Z * (1 - eps)  and  (S(n - 1) < p * Z * (1 + eps) or n == 1),
+ *     eps = 2^-16 + cols * 2^-39.
+ * The first term bounds the float32 error of a weight.  Its exponent (x_i - m)
+ * * (1 / T) carries three roundings, at most |d| * 3 * 2^-24 for d = (x_i - m)
+ * / T; only |d| <= 27 matters, since exp(-27) is below the fixed point's
+ * quantum 2^-39, which makes about 5e-6; a few ulp of expf (2^-22 or so) come
+ * on top, and 2^-16 = 1.5e-5 covers both.  The second term is the quantisation
+ * of `cols` weights to 2^-39 (half a quantum each, against Z >= 1), on both
+ * sides of the compare.
+ *
+ * Determinism is part of the contract: a row's n_r and threshold depend only
+ * on its keys, its length, p and T -- not on the plan (fused, any number of
+ * slices, any group size), the load path or the run.  Weights are only ever
+ * added as integers, which commute; no float atomic is used.  With cols <=
+ * 2^24 a sum stays below 2^63.
+ *
+ * kth_nucleus_wide_rows_*: d_n[r] = n_r; d_thr[r] = the n_r-th key of that
+ * order, the smallest kept logit: the bit pattern of an input element, a NaN
+ * written canonical, the zero word for an empty row.  Either may be NULL, not
+ * both.
+ * kth_topp_wide_rows_*: a top-k cap and the nucleus jointly, both on the
+ * unrenormalised row.  The outputs are bit for bit what the var top-k writes
+ * with largest = 1, the same k and d_lens, and d_ks[r] = min(n_r, cap_r):
+ * values and columns in column order, the padding (index -1, the zero word)
+ * and d_cnt.  cap_r = clamp(d_ks[r], 0, k), or k when d_ks is NULL; 1 <= k <=
+ * cols.  d_vals and d_idx may each be NULL, not both; d_cnt may be NULL.
+ * "Top-k first, then top-p on the renormalised rest" is a different filter and
+ * is not offered.
+ *
+ * Everything else is the wide-rows contract: asynchronous on the ctx stream, no
+ * host synchronisation, no allocation once kth_ctx_reserve_topp_rows (which
+ * covers the var top-k's scratch too) or an earlier call of that shape has
+ * run, graph-capturable under the conditions written at kth_select_i32_async
+ * -- a replay sees what d_ps, d_temps, d_lens and d_ks hold at replay time.
+ * Scratch of its own in the ctx, left as found, groups of rows keeping it at
+ * or below 32 MiB, so these calls and every other call may alternate on one
+ * ctx; kth_ctx_last_stats is unaffected; kth_ctx_wide_rows_force forces this
+ * plan too.
+ * KTH_EINVAL before any device work, outputs untouched: a NULL ctx or keys, no
+ * output pointer, rows < 0, a bad cols, ld, k, temp or kind, a NaN host p when
+ * d_ps is NULL.  rows == 0 returns KTH_OK and launches nothing.  KTH_ENODEV
+ * without a GPU.  (csrc/kth_rows_topp.hpp.) */
+int kth_nucleus_wide_rows_f32(kth_ctx *ctx, const float *d_keys, int64_t rows, int32_t cols, int64_t ld,
+                              const int32_t *d_lens, const float *d_ps, float p, const float *d_temps, float temp,
+                              int32_t *d_n, float *d_thr);
+int kth_nucleus_wide_rows_k16(kth_ctx *ctx, const void *d_keys, int64_t rows, int32_t cols, int64_t ld,
+                              const int32_t *d_lens, const float *d_ps, float p, const float *d_temps, float temp,
+                              int kind, int32_t *d_n, uint16_t *d_thr);
+int kth_topp_wide_rows_f32(kth_ctx *ctx, const float *d_keys, int64_t rows, int32_t cols, int64_t ld,
+                           const int32_t *d_lens, const int32_t *d_ks, int32_t k, const float *d_ps, float p,
+                           const float *d_temps, float temp, float *d_vals, int32_t *d_idx, int32_t *d_cnt);
+int kth_topp_wide_rows_k16(kth_ctx *ctx, const void *d_keys, int64_t rows, int32_t cols, int64_t ld,
+                           const int32_t *d_lens, const int32_t *d_ks, int32_t k, const float *d_ps, float p,
+                           const float *d_temps, float temp, int kind, uint16_t *d_vals, int32_t *d_idx,
+                           int32_t *d_cnt);
+int kth_ctx_reserve_topp_rows(kth_ctx *ctx, int64_t rows, int32_t cols);
+
 /* --- sharded selection, one process per GPU (TODO-kth-problem-cgm.c:76-278) --
  * The CGM rounds (local median :125-131, Gather :135-136, weighted median
  * :139-165, Bcast :168, 3-way count :171-185, Allreduce :190, discard

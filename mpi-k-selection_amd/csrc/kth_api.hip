@@ -212,6 +212,13 @@ struct kth_ctx {
     DevBuf<uint32_t> wide_cnt;
     bool wide_dirty = false;   // a wide-rows sequence was cut short: re-zero its scratch
     int32_t wide_force_slices = 0, wide_force_group = 0;  // kth_ctx_wide_rows_force (0: automatic)
+    // wide rows, top-p: a row's masses, counts and state (split form; zero between calls but
+    // for the state's overwritten words), and the ranks kth_topp_* hands to the var top-k
+    DevBuf<u64> tp_mass;
+    DevBuf<uint32_t> tp_cnt;
+    DevBuf<kth::TpState> tp_state;
+    DevBuf<int32_t> tp_rank;
+    bool tp_dirty = false;     // a top-p sequence was cut short: re-zero its scratch
     // timing: event pairs around the streaming pass and around whole selects
     bool timing = false;
     std::vector<hipEvent_t> ev_main, ev_total;
@@ -1139,6 +1146,123 @@ int wide16_rows_entry(kth_ctx *c, const void *d_keys, int64_t rows, int32_t cols
     return launch_wide16_rows<0, TOPK, VAR>(c, p, keys, rows, C, (u64)ld, K, flip2, kind, d_out, d_vals, d_idx, var);
 }
 
+// Top-p rows (kth_rows_topp.hpp).  The wide-rows plan; the split form's scratch
+// is the top-p calls' own, 24 KiB of bins and a state a row, so a group is
+// smaller than the wide select's.
+constexpr int64_t TP_ROW_BYTES = (int64_t)kth::NBINS * 12 + kth::TP_STATE_BYTES;
+constexpr int64_t TP_GROUP_MAX = WIDE_SCRATCH_MAX / TP_ROW_BYTES;  // 1362 rows
+
+// The split form's scratch for groups of g rows; new buffers are zeroed.
+int reserve_topp(kth_ctx *c, int64_t g) {
+    const u64 had_mass = c->tp_mass.count, had_cnt = c->tp_cnt.count, had_state = c->tp_state.count;
+    int rc = c->tp_mass.reserve((u64)g * kth::NBINS);
+    if (rc == KTH_OK) rc = c->tp_cnt.reserve((u64)g * kth::NBINS);
+    if (rc == KTH_OK) rc = c->tp_state.reserve((u64)g);
+    if (rc != KTH_OK) {
+        release_all(c->tp_mass, c->tp_cnt, c->tp_state);
+        return rc;
+    }
+    if (c->tp_mass.count != had_mass || c->tp_dirty)
+        HIP_TRY(hipMemsetAsync(c->tp_mass.p, 0, c->tp_mass.count * sizeof(u64), c->stream));
+    if (c->tp_cnt.count != had_cnt || c->tp_dirty)
+        HIP_TRY(hipMemsetAsync(c->tp_cnt.p, 0, c->tp_cnt.count * sizeof(uint32_t), c->stream));
+    if (c->tp_state.count != had_state || c->tp_dirty)
+        HIP_TRY(hipMemsetAsync(c->tp_state.p, 0, c->tp_state.count * sizeof(kth::TpState), c->stream));
+    c->tp_dirty = false;
+    return KTH_OK;
+}
+
+// One group of g rows: the fused launch, or the split form's sequence -- pass M,
+// then per digit a weighted count and a pick.  v, d_n, d_thr, rank: at the
+// group's first row.
+template <class K, bool VEC>
+int launch_topp_group(kth_ctx *c, const WidePlan &p, const typename K::elem *keys, int64_t g, uint32_t cols, u64 ld,
+                      const kth::TopP &v, int32_t *d_n, typename K::elem *d_thr, int32_t *rank) {
+    if (p.slices == 1) {
+        kth::k_tp_fused<K, VEC><<<(int)g, kth::WD_FBLOCK, 0, c->stream>>>(keys, ld, cols, v, d_n, d_thr, rank);
+        return launch_check();
+    }
+    const dim3 grid((unsigned)p.slices, (unsigned)g);
+    const uint32_t sk = (uint32_t)p.slice_keys;
+    kth::k_tp_max<K, VEC><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, c->tp_state.p, v);
+    for (int pass = 0; pass < K::PASSES; ++pass) {
+        kth::k_tp_count<K, VEC><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, pass, c->tp_mass.p, c->tp_cnt.p,
+                                                                    c->tp_state.p, v);
+        kth::k_tp_pick<K><<<(int)g, kth::WD_BLOCK, 0, c->stream>>>(c->tp_mass.p, c->tp_cnt.p, c->tp_state.p, pass, cols, v,
+                                                                 d_n, d_thr, rank);
+    }
+    const int rc = launch_check();
+    if (rc != KTH_OK) c->tp_dirty = true;
+    return rc;
+}
+
+// The nucleus of every row: plan, scratch and the loop over row groups.  The
+// arguments have been checked.  rank (kth_topp_*): rows int32, min(n_r, cap_r).
+template <class K>
+int topp_rows(kth_ctx *c, const typename K::elem *keys, int64_t rows, int32_t cols, int64_t ld, const kth::TopP &var,
+              int32_t *d_n, typename K::elem *d_thr, int32_t *rank) {
+    constexpr int32_t align = K::PER;  // 4 columns of 4-byte keys, 8 of 2-byte keys: 16 bytes
+    WidePlan p = wide_plan(rows, cols, c->num_cu, c->wide_force_slices, c->wide_force_group, align,
+                           align == 8 ? WIDE16_MIN_SLICE : WIDE_MIN_SLICE);
+    if (p.slices > 1) {
+        p.group_rows = (int32_t)std::min<int64_t>(p.group_rows, TP_GROUP_MAX);
+        KTH_TRY(reserve_topp(c, p.group_rows));
+    }
+    const bool vec = (reinterpret_cast<uintptr_t>(keys) & 15u) == 0 && ld % align == 0;
+    const auto launch = vec ? launch_topp_group<K, true> : launch_topp_group<K, false>;
+    for (int64_t r0 = 0; r0 < rows; r0 += p.group_rows) {
+        const int64_t g = std::min<int64_t>(p.group_rows, rows - r0);
+        kth::TopP v = var;
+        if (v.lens) v.lens += r0;
+        if (v.ps) v.ps += r0;
+        if (v.temps) v.temps += r0;
+        if (v.ks) v.ks += r0;
+        KTH_TRY(launch(c, p, keys + (u64)r0 * (u64)ld, g, (uint32_t)cols, (u64)ld, v, d_n ? d_n + r0 : nullptr,
+                       d_thr ? d_thr + r0 : nullptr, rank ? rank + r0 : nullptr));
+    }
+    return KTH_OK;
+}
+
+// The four top-p entry points: the argument check, then the nucleus and, for
+// kth_topp_* (TOPK), the var top-k sequence with the ranks the last pick wrote.
+// kind: a KTH_K16_* float kind, or -1 for float32 keys.
+template <bool TOPK>
+int topp_entry(kth_ctx *c, const void *d_keys, int64_t rows, int32_t cols, int64_t ld, const int32_t *d_lens,
+               const int32_t *d_ks, int32_t k, const float *d_ps, float p, const float *d_temps, float temp, int kind,
+               int32_t *d_n, void *d_thr, void *d_vals, int32_t *d_idx, int32_t *d_cnt) {
+    const bool has_out = TOPK ? d_vals || d_idx : d_n || d_thr;
+    if (!c || !d_keys || !has_out || rows < 0 || cols < 1 || cols > KTH_WIDE_MAX_COLS || ld < cols) return KTH_EINVAL;
+    if (TOPK && (k < 1 || k > cols)) return KTH_EINVAL;
+    if (kind != -1 && kind != KTH_K16_F16 && kind != KTH_K16_BF16) return KTH_EINVAL;
+    if (!(temp > 0.0f) || !std::isfinite(temp) || (!d_ps && std::isnan(p))) return KTH_EINVAL;
+    if (rows == 0) return KTH_OK;
+    KTH_TRY(set_device(c));
+    int32_t *rank = nullptr;
+    if (TOPK) {
+        KTH_TRY(c->tp_rank.reserve((u64)rows));
+        rank = c->tp_rank.p;
+    }
+    const kth::TopP var{d_lens, d_ps, d_temps, TOPK ? d_ks : nullptr, p, temp, TOPK ? k : 0};
+    if (kind == -1) {
+        KTH_TRY(topp_rows<kth::TpF32>(c, static_cast<const uint32_t *>(d_keys), rows, cols, ld, var, d_n,
+                                      static_cast<uint32_t *>(d_thr), rank));
+        if (TOPK)
+            return wide_rows_entry<true, true, true>(c, d_keys, rows, cols, ld, k, nullptr, 1, d_vals, d_idx,
+                                                     kth::WideVar{d_lens, rank, d_cnt});
+        return KTH_OK;
+    }
+    const uint16_t *keys = static_cast<const uint16_t *>(d_keys);
+    uint16_t *thr = static_cast<uint16_t *>(d_thr);
+    if (kind == KTH_K16_BF16)
+        KTH_TRY(topp_rows<kth::TpK16<true>>(c, keys, rows, cols, ld, var, d_n, thr, rank));
+    else
+        KTH_TRY(topp_rows<kth::TpK16<false>>(c, keys, rows, cols, ld, var, d_n, thr, rank));
+    if (TOPK)
+        return wide16_rows_entry<true, true>(c, d_keys, rows, cols, ld, k, kind, nullptr, 1,
+                                             static_cast<uint16_t *>(d_vals), d_idx, kth::WideVar{d_lens, rank, d_cnt});
+    return KTH_OK;
+}
+
 // ------------------------------------------------------- ctx creation, in parts
 // Every tuning variable of a ctx (design exploration and A/B runs; unset: the
 // defaults in kth_ctx).  Needs c->num_cu.  Read elsewhere: KTH_STAMPS (the
@@ -1381,7 +1505,7 @@ int kth_ctx_destroy(kth_ctx *c) {
     if (c->islots) (void)hipFree(c->islots);
     release_all(c->sample, c->cand, c->gdir, c->cand_rows, c->tk_segv, c->tk_segp, c->tk_wcnt, c->tk_wstart, c->staging,
                 c->topk, c->mstate, c->mslots, c->mcand, c->k16, c->k16st, c->tk16_nread, c->wide_hist, c->wide_state,
-                c->wide_cnt);
+                c->wide_cnt, c->tp_mass, c->tp_cnt, c->tp_state, c->tp_rank);
     if (c->d_mstatus) (void)hipFree(c->d_mstatus);
     if (c->h_mstatus) (void)hipHostFree(c->h_mstatus);
     if (c->d_status) (void)hipFree(c->d_status);
@@ -2272,6 +2396,46 @@ int kth_topk_wide_rows_var_k16(kth_ctx *c, const void *d_keys, int64_t rows, int
                                uint16_t *d_vals, int32_t *d_idx, int32_t *d_cnt) {
     return wide16_rows_entry<true, true>(c, d_keys, rows, cols, ld, k, kind, nullptr, largest, d_vals, d_idx,
                                          kth::WideVar{d_lens, d_ks, d_cnt});
+}
+
+int kth_nucleus_wide_rows_f32(kth_ctx *c, const float *d_keys, int64_t rows, int32_t cols, int64_t ld,
+                              const int32_t *d_lens, const float *d_ps, float p, const float *d_temps, float temp,
+                              int32_t *d_n, float *d_thr) {
+    return topp_entry<false>(c, d_keys, rows, cols, ld, d_lens, nullptr, 0, d_ps, p, d_temps, temp, -1, d_n, d_thr,
+                             nullptr, nullptr, nullptr);
+}
+
+int kth_nucleus_wide_rows_k16(kth_ctx *c, const void *d_keys, int64_t rows, int32_t cols, int64_t ld,
+                              const int32_t *d_lens, const float *d_ps, float p, const float *d_temps, float temp,
+                              int kind, int32_t *d_n, uint16_t *d_thr) {
+    if (kind < KTH_K16_I16 || kind > KTH_K16_BF16) return KTH_EINVAL;
+    return topp_entry<false>(c, d_keys, rows, cols, ld, d_lens, nullptr, 0, d_ps, p, d_temps, temp, kind, d_n, d_thr,
+                             nullptr, nullptr, nullptr);
+}
+
+int kth_topp_wide_rows_f32(kth_ctx *c, const float *d_keys, int64_t rows, int32_t cols, int64_t ld,
+                           const int32_t *d_lens, const int32_t *d_ks, int32_t k, const float *d_ps, float p,
+                           const float *d_temps, float temp, float *d_vals, int32_t *d_idx, int32_t *d_cnt) {
+    return topp_entry<true>(c, d_keys, rows, cols, ld, d_lens, d_ks, k, d_ps, p, d_temps, temp, -1, nullptr, nullptr,
+                            d_vals, d_idx, d_cnt);
+}
+
+int kth_topp_wide_rows_k16(kth_ctx *c, const void *d_keys, int64_t rows, int32_t cols, int64_t ld,
+                           const int32_t *d_lens, const int32_t *d_ks, int32_t k, const float *d_ps, float p,
+                           const float *d_temps, float temp, int kind, uint16_t *d_vals, int32_t *d_idx,
+                           int32_t *d_cnt) {
+    if (kind < KTH_K16_I16 || kind > KTH_K16_BF16) return KTH_EINVAL;
+    return topp_entry<true>(c, d_keys, rows, cols, ld, d_lens, d_ks, k, d_ps, p, d_temps, temp, kind, nullptr, nullptr,
+                            d_vals, d_idx, d_cnt);
+}
+
+int kth_ctx_reserve_topp_rows(kth_ctx *c, int64_t rows, int32_t cols) {
+    if (!c || rows < 0 || cols < 1 || cols > KTH_WIDE_MAX_COLS) return KTH_EINVAL;
+    KTH_TRY(set_device(c));
+    // the split form of both sequences whatever the plan of (rows, cols) is: a forced plan then fits too
+    KTH_TRY(reserve_topp(c, std::min(std::max<int64_t>(rows, 1), TP_GROUP_MAX)));
+    KTH_TRY(c->tp_rank.reserve((u64)std::max<int64_t>(rows, 1)));
+    return reserve_wide(c, std::min(std::max<int64_t>(rows, 1), WIDE_GROUP_MAX));
 }
 
 }  // extern "C"

@@ -2045,3 +2045,5 @@ __global__ __launch_bounds__(BLK) void k_state_bcast(const SelState *src, StateP
 #include "kth_rows16.hpp"
 #include "kth_rows_wide.hpp"
 #include "kth_rows_wide16.hpp"
+#include "kth_rows_topp.hpp"
+#include "kth_rows_topp16.hpp"

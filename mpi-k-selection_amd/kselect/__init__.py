@@ -568,6 +568,82 @@ class Selector:
                                              int(k), 1 if largest else 0, kind, _ptr_or_none(d_vals),
                                              _ptr_or_none(d_idx), _ptr_or_none(d_cnt)), "kth_topk_wide_rows_var_k16")
 
+    def nucleus_rows_wide(self, d_keys, rows, cols, d_n=None, d_thr=None, p=1.0, temp=1.0, d_lens=None, d_ps=None,
+                          d_temps=None, ld=None):
+        """The top-p nucleus of every row of a float32 matrix
+        (kth_nucleus_wide_rows_f32): d_n[r] = the number of the largest logits
+        whose softmax mass (at temperature T_r) reaches p_r, d_thr[r] = the
+        smallest of them.  d_ps, d_temps: `rows` float32 device elements, None:
+        the scalars p / temp for every row; d_lens as in rows_wide_var.
+        d_n (int32) and d_thr (float32) may each be None, not both."""
+        _need_f32(d_keys, "d_keys")
+        _need_f32(d_thr, "d_thr")
+        _need_i32(d_n, "d_n")
+        _need_i32(d_lens, "d_lens")
+        _need_f32(d_ps, "d_ps")
+        _need_f32(d_temps, "d_temps")
+        check(LIB.kth_nucleus_wide_rows_f32(self._ctx, _ptr(d_keys), int(rows), int(cols),
+                                            int(cols if ld is None else ld), _ptr_or_none(d_lens), _ptr_or_none(d_ps),
+                                            float(p), _ptr_or_none(d_temps), float(temp), _ptr_or_none(d_n),
+                                            _ptr_or_none(d_thr)), "kth_nucleus_wide_rows_f32")
+
+    def nucleus_rows_wide16(self, d_keys, rows, cols, d_n=None, d_thr=None, p=1.0, temp=1.0, kind=None, d_lens=None,
+                            d_ps=None, d_temps=None, ld=None):
+        """nucleus_rows_wide for float16 / bfloat16 rows (kth_nucleus_wide_rows_k16)."""
+        kind = _k16_kind(d_keys, kind, "d_keys")
+        if d_thr is not None:
+            _k16_same_kind(d_keys, d_thr, kind, "d_thr")
+        _need_i32(d_n, "d_n")
+        _need_i32(d_lens, "d_lens")
+        _need_f32(d_ps, "d_ps")
+        _need_f32(d_temps, "d_temps")
+        check(LIB.kth_nucleus_wide_rows_k16(self._ctx, _ptr(d_keys), int(rows), int(cols),
+                                            int(cols if ld is None else ld), _ptr_or_none(d_lens), _ptr_or_none(d_ps),
+                                            float(p), _ptr_or_none(d_temps), float(temp), kind, _ptr_or_none(d_n),
+                                            _ptr_or_none(d_thr)), "kth_nucleus_wide_rows_k16")
+
+    def topp_rows_wide(self, d_keys, rows, cols, k, d_vals=None, d_idx=None, p=1.0, temp=1.0, d_lens=None, d_ks=None,
+                       d_ps=None, d_temps=None, d_cnt=None, ld=None):
+        """Top-k cap and top-p nucleus of every float32 row in one call
+        (kth_topp_wide_rows_f32): the outputs of topk_rows_wide_var(largest=True)
+        with each row's rank min(n_r, clamp(d_ks[r], 0, k)), n_r the nucleus size
+        of nucleus_rows_wide.  k is the output stride."""
+        _need_f32(d_keys, "d_keys")
+        _need_f32(d_vals, "d_vals")
+        _need_i32(d_idx, "d_idx")
+        _need_i32(d_lens, "d_lens")
+        _need_i32(d_ks, "d_ks")
+        _need_i32(d_cnt, "d_cnt")
+        _need_f32(d_ps, "d_ps")
+        _need_f32(d_temps, "d_temps")
+        check(LIB.kth_topp_wide_rows_f32(self._ctx, _ptr(d_keys), int(rows), int(cols), int(cols if ld is None else ld),
+                                         _ptr_or_none(d_lens), _ptr_or_none(d_ks), int(k), _ptr_or_none(d_ps), float(p),
+                                         _ptr_or_none(d_temps), float(temp), _ptr_or_none(d_vals), _ptr_or_none(d_idx),
+                                         _ptr_or_none(d_cnt)), "kth_topp_wide_rows_f32")
+
+    def topp_rows_wide16(self, d_keys, rows, cols, k, d_vals=None, d_idx=None, p=1.0, temp=1.0, kind=None, d_lens=None,
+                         d_ks=None, d_ps=None, d_temps=None, d_cnt=None, ld=None):
+        """topp_rows_wide for float16 / bfloat16 rows (kth_topp_wide_rows_k16)."""
+        kind = _k16_kind(d_keys, kind, "d_keys")
+        if d_vals is not None:
+            _k16_same_kind(d_keys, d_vals, kind, "d_vals")
+        _need_i32(d_idx, "d_idx")
+        _need_i32(d_lens, "d_lens")
+        _need_i32(d_ks, "d_ks")
+        _need_i32(d_cnt, "d_cnt")
+        _need_f32(d_ps, "d_ps")
+        _need_f32(d_temps, "d_temps")
+        check(LIB.kth_topp_wide_rows_k16(self._ctx, _ptr(d_keys), int(rows), int(cols), int(cols if ld is None else ld),
+                                         _ptr_or_none(d_lens), _ptr_or_none(d_ks), int(k), _ptr_or_none(d_ps), float(p),
+                                         _ptr_or_none(d_temps), float(temp), kind, _ptr_or_none(d_vals),
+                                         _ptr_or_none(d_idx), _ptr_or_none(d_cnt)), "kth_topp_wide_rows_k16")
+
+    def reserve_topp_rows(self, rows, cols):
+        """Pre-size the scratch of the top-p calls, the var top-k's included
+        (kth_ctx_reserve_topp_rows): later calls of up to `rows` rows allocate
+        nothing."""
+        check(LIB.kth_ctx_reserve_topp_rows(self._ctx, int(rows), int(cols)), "kth_ctx_reserve_topp_rows")
+
     def reserve_wide_rows(self, rows, cols):
         """Pre-size the wide-rows scratch (kth_ctx_reserve_wide_rows): later
         calls of up to `rows` rows allocate nothing."""
