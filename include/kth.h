@@ -704,6 +704,85 @@ int kth_topp_wide_rows_k16(kth_ctx *ctx, const void *d_keys, int64_t rows, int32
                            int32_t *d_cnt);
 int kth_ctx_reserve_topp_rows(kth_ctx *ctx, int64_t rows, int32_t cols);
 
+/* --- wide rows, sampling: one token per row from the filtered distribution ------
+ * The sampler's last step: draw one column of each row from the softmax of its
+ * logits restricted to the top-k / top-p kept set.  The library holds no
+ * generator: the caller fills d_us with one uniform number a row (torch.rand,
+ * say), so that a graph replay draws afresh and a fixed u reproduces a token.
+ * Drawing is the weighted select the nucleus is, run against the running mass;
+ * the result is one int32 a row -- no rows * k output, no sort, no float sum
+ * whose order the hardware picks.  float32 rows (_f32) and float16 / bfloat16
+ * rows (_k16, kind KTH_K16_F16 or KTH_K16_BF16; the integer kinds are
+ * KTH_EINVAL).
+ *
+ * The row, its order (largest first, ties by column), the weights w_i, S(j), Z,
+ * len_r, p_r and T_r are exactly those of the top-p section above, with its
+ * clamps and its rows where m is +inf or NaN; d_lens, d_ps, d_temps as there.
+ *
+ * Cap.  c_r = d_ks[r], or the host k when d_ks is NULL (d_ks: `rows` int32 on
+ * the device, read when the launches run).  c_r <= 0 means no cap, the sampler
+ * convention for "top-k off" -- on purpose not that of kth_topp_*, where k is
+ * an output stride.  No upper bound is checked; a cap at or above len_r does
+ * not bind.
+ * Kept keys.  n_r = min(N_r, c_r), or N_r without a cap, where N_r is the
+ * nucleus size kth_nucleus_wide_rows_* returns for the same keys, length, p and
+ * T, bit for bit: the same fixed-point arithmetic, hence the same band.
+ * d_cnt[r] = n_r; d_cnt may be NULL.
+ * The number.  d_us is required: `rows` float32 on the device, 4-byte aligned,
+ * read only on the device when the launches run.  u_r = d_us[r]; NaN or a
+ * negative value counts as 0; a value of 1 or more selects the last kept key of
+ * non-zero weight (the clamp below).
+ * The token.  j_r is the least j >= 1 with S(j) > u_r * S(n_r); on the device,
+ * t = min(S_fix(n_r), floor(u_r * S_fix(n_r)) + 1), computed in double by one
+ * thread a row, then the least j with S_fix(j) >= t (S_fix: the 2^39 fixed-point
+ * sums of the top-p section).  t <= S_fix(n_r), so j_r <= n_r by integer
+ * arithmetic.  d_tok[r] = the column of the j_r-th key of the order -- a single
+ * column, since ties are ordered by column.  An empty row: d_tok[r] = -1 and
+ * d_cnt[r] = 0.  For u uniform on [0, 1) a kept key i is drawn with probability
+ * w_i / S(n_r); a key outside the kept set is never drawn, nor is a key of
+ * weight 0.
+ *
+ * Tolerance.  For the n returned, a call may return any j with 1 <= j <= n,
+ *     S(j) >= A (1 - e)  and  (j == 1 or S(j - 1) <= A (1 + e)),
+ *     A = u S(n) in exact arithmetic,  e = 2 * eps,  eps = 2^-16 + cols * 2^-39
+ * (the eps of the top-p section).  Derivation: the device compares S_fix(j)
+ * with u * S_fix(n).  Both sums carry the nucleus's weight error -- every
+ * float32 weight is within a factor (1 +- 2^-16) of its exact value -- and they
+ * stand on the two sides of the compare, so the relative errors add: 2 * 2^-16.
+ * The quantisation of a weight to 2^-39 is absolute, at most cols * 2^-40 a
+ * sum.  Where A <= 1 the first key decides (S(1) = 1 exactly on both sides, so
+ * j = 1 is returned and admitted); where A > 1 an absolute cols * 2^-40 on
+ * each side is at most a relative cols * 2^-39 in all, and the floor and the +1
+ * of t are two quanta more, far inside the same term.  Together e = 2 * 2^-16 +
+ * 2 * cols * 2^-39.
+ *
+ * Determinism is part of the contract: d_tok and d_cnt depend on the row's
+ * keys, length, p, T, cap and u only -- not on the plan (fused, any number of
+ * slices, any group size), the load path or the run.  Weights are only ever
+ * added as integers; no float atomic is used.
+ *
+ * Everything else is the wide-rows contract: asynchronous on the ctx stream, no
+ * host read of any device array, no allocation once
+ * kth_ctx_reserve_sample_rows or an earlier call of that shape has run,
+ * graph-capturable under the conditions written at kth_select_i32_async -- a
+ * replay sees what d_us, d_ps, d_temps, d_lens and d_ks hold at replay time.
+ * kth_ctx_wide_rows_force forces this plan too.  Scratch in the ctx (the top-p
+ * calls' bins and a state of its own), left as found, groups of rows keeping
+ * it at or below 32 MiB, so these calls and every other call may alternate on
+ * one ctx; kth_ctx_last_stats is unaffected.
+ * KTH_EINVAL before any device work, outputs untouched: a NULL ctx, keys, d_us
+ * or d_tok, rows < 0, a bad cols, ld, temp or kind, a NaN host p when d_ps is
+ * NULL.  rows == 0 returns KTH_OK and launches nothing.  KTH_ENODEV without a
+ * GPU.  (csrc/kth_rows_sample.hpp.) */
+int kth_sample_wide_rows_f32(kth_ctx *ctx, const float *d_keys, int64_t rows, int32_t cols, int64_t ld,
+                             const int32_t *d_lens, const int32_t *d_ks, int32_t k, const float *d_ps, float p,
+                             const float *d_temps, float temp, const float *d_us, int32_t *d_tok, int32_t *d_cnt);
+int kth_sample_wide_rows_k16(kth_ctx *ctx, const void *d_keys, int64_t rows, int32_t cols, int64_t ld,
+                             const int32_t *d_lens, const int32_t *d_ks, int32_t k, const float *d_ps, float p,
+                             const float *d_temps, float temp, const float *d_us, int kind, int32_t *d_tok,
+                             int32_t *d_cnt);
+int kth_ctx_reserve_sample_rows(kth_ctx *ctx, int64_t rows, int32_t cols);
+
 /* --- sharded selection, one process per GPU (TODO-kth-problem-cgm.c:76-278) --
  * The CGM rounds (local median :125-131, Gather :135-136, weighted median
  * :139-165, Bcast :168, 3-way count :171-185, Allreduce :190, discard

@@ -219,6 +219,11 @@ struct kth_ctx {
     DevBuf<kth::TpState> tp_state;
     DevBuf<int32_t> tp_rank;
     bool tp_dirty = false;     // a top-p sequence was cut short: re-zero its scratch
+    // wide rows, sampling (split form): a state per row of a group (its accumulating words zero
+    // between calls) and the equal keys of every slice; the bins are the top-p calls'
+    DevBuf<kth::SmState> sm_state;
+    DevBuf<uint32_t> sm_loc;
+    bool sm_dirty = false;     // a sample sequence was cut short: re-zero its state
     // timing: event pairs around the streaming pass and around whole selects
     bool timing = false;
     std::vector<hipEvent_t> ev_main, ev_total;
@@ -1263,6 +1268,105 @@ int topp_entry(kth_ctx *c, const void *d_keys, int64_t rows, int32_t cols, int64
     return KTH_OK;
 }
 
+// Sampling rows (kth_rows_sample.hpp).  The wide-rows plan; the split form adds a
+// state and a count per slice a row to the top-p calls' bins, so a group is a
+// little smaller than theirs.
+constexpr int64_t SM_ROW_BYTES = TP_ROW_BYTES + kth::SM_STATE_BYTES + 4 * (int64_t)kth::WD_MAX_SLICES;
+constexpr int64_t SM_GROUP_MAX = WIDE_SCRATCH_MAX / SM_ROW_BYTES;  // 1305 rows
+
+// The split form's scratch for groups of g rows; a new state buffer is zeroed.
+int reserve_sample(kth_ctx *c, int64_t g) {
+    KTH_TRY(reserve_topp(c, g));
+    const u64 had_state = c->sm_state.count;
+    int rc = c->sm_state.reserve((u64)g);
+    if (rc == KTH_OK) rc = c->sm_loc.reserve((u64)g * kth::WD_MAX_SLICES);
+    if (rc != KTH_OK) {
+        release_all(c->sm_state, c->sm_loc);
+        return rc;
+    }
+    if (c->sm_state.count != had_state || c->sm_dirty)
+        HIP_TRY(hipMemsetAsync(c->sm_state.p, 0, c->sm_state.count * sizeof(kth::SmState), c->stream));
+    c->sm_dirty = false;
+    return KTH_OK;
+}
+
+// One group of g rows: the fused launch, or the split form's sequence -- pass M,
+// per digit of descent A and of descent B a weighted count and a pick, then the
+// locate's count and pick.  no_a: the host arguments alone say that no row
+// needs descent A (no filter at all).  v, us, d_tok, d_cnt: at the group's first row.
+template <class K, bool VEC>
+int launch_sample_group(kth_ctx *c, const WidePlan &p, const typename K::elem *keys, int64_t g, uint32_t cols, u64 ld,
+                        const kth::TopP &v, bool no_a, const float *us, int32_t *d_tok, int32_t *d_cnt) {
+    if (p.slices == 1) {
+        kth::k_sm_fused<K, VEC><<<(int)g, kth::WD_FBLOCK, 0, c->stream>>>(keys, ld, cols, v, us, d_tok, d_cnt);
+        return launch_check();
+    }
+    const dim3 grid((unsigned)p.slices, (unsigned)g);
+    const uint32_t sk = (uint32_t)p.slice_keys;
+    kth::k_sm_max<K, VEC><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, c->sm_state.p, v);
+    for (int phase = no_a ? 1 : 0; phase < 2; ++phase)
+        for (int pass = 0; pass < K::PASSES; ++pass) {
+            kth::k_sm_count<K, VEC><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, phase, pass, c->tp_mass.p,
+                                                                        c->tp_cnt.p, c->sm_state.p, v);
+            kth::k_sm_pick<K><<<(int)g, kth::WD_BLOCK, 0, c->stream>>>(c->tp_mass.p, c->tp_cnt.p, c->sm_state.p, phase, pass,
+                                                                     cols, v, us);
+        }
+    kth::k_sm_loc_count<K, VEC><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, c->sm_state.p, c->sm_loc.p, v);
+    kth::k_sm_loc_pick<K, VEC><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, c->sm_state.p, c->sm_loc.p, v,
+                                                                   d_tok, d_cnt);
+    const int rc = launch_check();
+    if (rc != KTH_OK) c->tp_dirty = c->sm_dirty = true;
+    return rc;
+}
+
+// One token of every row: plan, scratch and the loop over row groups.  The
+// arguments have been checked.
+template <class K>
+int sample_rows(kth_ctx *c, const typename K::elem *keys, int64_t rows, int32_t cols, int64_t ld, const kth::TopP &var,
+                bool no_a, const float *d_us, int32_t *d_tok, int32_t *d_cnt) {
+    constexpr int32_t align = K::PER;
+    WidePlan p = wide_plan(rows, cols, c->num_cu, c->wide_force_slices, c->wide_force_group, align,
+                           align == 8 ? WIDE16_MIN_SLICE : WIDE_MIN_SLICE);
+    if (p.slices > 1) {
+        p.group_rows = (int32_t)std::min<int64_t>(p.group_rows, SM_GROUP_MAX);
+        KTH_TRY(reserve_sample(c, p.group_rows));
+    }
+    const bool vec = (reinterpret_cast<uintptr_t>(keys) & 15u) == 0 && ld % align == 0;
+    const auto launch = vec ? launch_sample_group<K, true> : launch_sample_group<K, false>;
+    for (int64_t r0 = 0; r0 < rows; r0 += p.group_rows) {
+        const int64_t g = std::min<int64_t>(p.group_rows, rows - r0);
+        kth::TopP v = var;
+        if (v.lens) v.lens += r0;
+        if (v.ps) v.ps += r0;
+        if (v.temps) v.temps += r0;
+        if (v.ks) v.ks += r0;
+        KTH_TRY(launch(c, p, keys + (u64)r0 * (u64)ld, g, (uint32_t)cols, (u64)ld, v, no_a, d_us + r0, d_tok + r0,
+                       d_cnt ? d_cnt + r0 : nullptr));
+    }
+    return KTH_OK;
+}
+
+// The two sample entry points: the argument check, then the rows.  kind: a
+// KTH_K16_* float kind, or -1 for float32 keys.
+int sample_entry(kth_ctx *c, const void *d_keys, int64_t rows, int32_t cols, int64_t ld, const int32_t *d_lens,
+                 const int32_t *d_ks, int32_t k, const float *d_ps, float p, const float *d_temps, float temp,
+                 const float *d_us, int kind, int32_t *d_tok, int32_t *d_cnt) {
+    if (!c || !d_keys || !d_us || !d_tok || rows < 0 || cols < 1 || cols > KTH_WIDE_MAX_COLS || ld < cols)
+        return KTH_EINVAL;
+    if (kind != -1 && kind != KTH_K16_F16 && kind != KTH_K16_BF16) return KTH_EINVAL;
+    if (!(temp > 0.0f) || !std::isfinite(temp) || (!d_ps && std::isnan(p))) return KTH_EINVAL;
+    if (rows == 0) return KTH_OK;
+    KTH_TRY(set_device(c));
+    const kth::TopP var{d_lens, d_ps, d_temps, d_ks, p, temp, k};
+    const bool no_a = !d_ps && p >= 1.0f && !d_ks && k <= 0;
+    if (kind == -1)
+        return sample_rows<kth::TpF32>(c, static_cast<const uint32_t *>(d_keys), rows, cols, ld, var, no_a, d_us, d_tok,
+                                       d_cnt);
+    const uint16_t *keys = static_cast<const uint16_t *>(d_keys);
+    if (kind == KTH_K16_BF16) return sample_rows<kth::TpK16<true>>(c, keys, rows, cols, ld, var, no_a, d_us, d_tok, d_cnt);
+    return sample_rows<kth::TpK16<false>>(c, keys, rows, cols, ld, var, no_a, d_us, d_tok, d_cnt);
+}
+
 // ------------------------------------------------------- ctx creation, in parts
 // Every tuning variable of a ctx (design exploration and A/B runs; unset: the
 // defaults in kth_ctx).  Needs c->num_cu.  Read elsewhere: KTH_STAMPS (the
@@ -1505,7 +1609,7 @@ int kth_ctx_destroy(kth_ctx *c) {
     if (c->islots) (void)hipFree(c->islots);
     release_all(c->sample, c->cand, c->gdir, c->cand_rows, c->tk_segv, c->tk_segp, c->tk_wcnt, c->tk_wstart, c->staging,
                 c->topk, c->mstate, c->mslots, c->mcand, c->k16, c->k16st, c->tk16_nread, c->wide_hist, c->wide_state,
-                c->wide_cnt, c->tp_mass, c->tp_cnt, c->tp_state, c->tp_rank);
+                c->wide_cnt, c->tp_mass, c->tp_cnt, c->tp_state, c->tp_rank, c->sm_state, c->sm_loc);
     if (c->d_mstatus) (void)hipFree(c->d_mstatus);
     if (c->h_mstatus) (void)hipHostFree(c->h_mstatus);
     if (c->d_status) (void)hipFree(c->d_status);
@@ -2436,6 +2540,27 @@ int kth_ctx_reserve_topp_rows(kth_ctx *c, int64_t rows, int32_t cols) {
     KTH_TRY(reserve_topp(c, std::min(std::max<int64_t>(rows, 1), TP_GROUP_MAX)));
     KTH_TRY(c->tp_rank.reserve((u64)std::max<int64_t>(rows, 1)));
     return reserve_wide(c, std::min(std::max<int64_t>(rows, 1), WIDE_GROUP_MAX));
+}
+
+int kth_sample_wide_rows_f32(kth_ctx *c, const float *d_keys, int64_t rows, int32_t cols, int64_t ld,
+                             const int32_t *d_lens, const int32_t *d_ks, int32_t k, const float *d_ps, float p,
+                             const float *d_temps, float temp, const float *d_us, int32_t *d_tok, int32_t *d_cnt) {
+    return sample_entry(c, d_keys, rows, cols, ld, d_lens, d_ks, k, d_ps, p, d_temps, temp, d_us, -1, d_tok, d_cnt);
+}
+
+int kth_sample_wide_rows_k16(kth_ctx *c, const void *d_keys, int64_t rows, int32_t cols, int64_t ld,
+                             const int32_t *d_lens, const int32_t *d_ks, int32_t k, const float *d_ps, float p,
+                             const float *d_temps, float temp, const float *d_us, int kind, int32_t *d_tok,
+                             int32_t *d_cnt) {
+    if (kind < KTH_K16_I16 || kind > KTH_K16_BF16) return KTH_EINVAL;
+    return sample_entry(c, d_keys, rows, cols, ld, d_lens, d_ks, k, d_ps, p, d_temps, temp, d_us, kind, d_tok, d_cnt);
+}
+
+int kth_ctx_reserve_sample_rows(kth_ctx *c, int64_t rows, int32_t cols) {
+    if (!c || rows < 0 || cols < 1 || cols > KTH_WIDE_MAX_COLS) return KTH_EINVAL;
+    KTH_TRY(set_device(c));
+    // the split form whatever the plan of (rows, cols) is: a forced plan then fits too
+    return reserve_sample(c, std::min(std::max<int64_t>(rows, 1), SM_GROUP_MAX));
 }
 
 }  // extern "C"

@@ -644,6 +644,49 @@ class Selector:
         nothing."""
         check(LIB.kth_ctx_reserve_topp_rows(self._ctx, int(rows), int(cols)), "kth_ctx_reserve_topp_rows")
 
+    def sample_rows_wide(self, d_keys, rows, cols, d_us, d_tok, k=0, p=1.0, temp=1.0, d_lens=None, d_ks=None,
+                         d_ps=None, d_temps=None, d_cnt=None, ld=None):
+        """One token per float32 row drawn from the top-k / top-p filtered
+        softmax (kth_sample_wide_rows_f32): d_tok[r] = the column at which the
+        running mass of the kept keys, largest first and ties by column, passes
+        d_us[r] times their total; d_cnt[r] = how many keys were kept,
+        min(nucleus size, cap).  d_us: `rows` float32 device elements the caller
+        draws, uniform on [0, 1).  k / d_ks: the cap, <= 0 for none; p / d_ps,
+        temp / d_temps, d_lens as in nucleus_rows_wide.  d_cnt may be None."""
+        _need_f32(d_keys, "d_keys")
+        _need_f32(d_us, "d_us")
+        _need_i32(d_tok, "d_tok")
+        _need_i32(d_lens, "d_lens")
+        _need_i32(d_ks, "d_ks")
+        _need_i32(d_cnt, "d_cnt")
+        _need_f32(d_ps, "d_ps")
+        _need_f32(d_temps, "d_temps")
+        check(LIB.kth_sample_wide_rows_f32(self._ctx, _ptr(d_keys), int(rows), int(cols), int(cols if ld is None else ld),
+                                           _ptr_or_none(d_lens), _ptr_or_none(d_ks), int(k), _ptr_or_none(d_ps),
+                                           float(p), _ptr_or_none(d_temps), float(temp), _ptr(d_us), _ptr(d_tok),
+                                           _ptr_or_none(d_cnt)), "kth_sample_wide_rows_f32")
+
+    def sample_rows_wide16(self, d_keys, rows, cols, d_us, d_tok, k=0, p=1.0, temp=1.0, kind=None, d_lens=None,
+                           d_ks=None, d_ps=None, d_temps=None, d_cnt=None, ld=None):
+        """sample_rows_wide for float16 / bfloat16 rows (kth_sample_wide_rows_k16)."""
+        kind = _k16_kind(d_keys, kind, "d_keys")
+        _need_f32(d_us, "d_us")
+        _need_i32(d_tok, "d_tok")
+        _need_i32(d_lens, "d_lens")
+        _need_i32(d_ks, "d_ks")
+        _need_i32(d_cnt, "d_cnt")
+        _need_f32(d_ps, "d_ps")
+        _need_f32(d_temps, "d_temps")
+        check(LIB.kth_sample_wide_rows_k16(self._ctx, _ptr(d_keys), int(rows), int(cols), int(cols if ld is None else ld),
+                                           _ptr_or_none(d_lens), _ptr_or_none(d_ks), int(k), _ptr_or_none(d_ps),
+                                           float(p), _ptr_or_none(d_temps), float(temp), _ptr(d_us), kind, _ptr(d_tok),
+                                           _ptr_or_none(d_cnt)), "kth_sample_wide_rows_k16")
+
+    def reserve_sample_rows(self, rows, cols):
+        """Pre-size the scratch of the sample calls (kth_ctx_reserve_sample_rows):
+        later calls of up to `rows` rows allocate nothing."""
+        check(LIB.kth_ctx_reserve_sample_rows(self._ctx, int(rows), int(cols)), "kth_ctx_reserve_sample_rows")
+
     def reserve_wide_rows(self, rows, cols):
         """Pre-size the wide-rows scratch (kth_ctx_reserve_wide_rows): later
         calls of up to `rows` rows allocate nothing."""

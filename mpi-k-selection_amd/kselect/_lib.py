@@ -180,6 +180,13 @@ PROTOS = {
                                               ctypes.c_int32, c_vp, ctypes.c_float, c_vp, ctypes.c_float, ctypes.c_int,
                                               c_vp, c_vp, c_vp]),
     "kth_ctx_reserve_topp_rows": (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int32]),
+    "kth_sample_wide_rows_f32": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, c_vp, c_vp,
+                                                ctypes.c_int32, c_vp, ctypes.c_float, c_vp, ctypes.c_float, c_vp, c_vp,
+                                                c_vp]),
+    "kth_sample_wide_rows_k16": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, c_vp, c_vp,
+                                                ctypes.c_int32, c_vp, ctypes.c_float, c_vp, ctypes.c_float, c_vp,
+                                                ctypes.c_int, c_vp, c_vp]),
+    "kth_ctx_reserve_sample_rows": (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int32]),
     "kth_topk_i32": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, c_vp, c_vp]),
     "kth_topk_f32": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, c_vp, c_vp]),
     "kth_topk_k16": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
