@@ -928,15 +928,16 @@ struct WidePlan {
     int64_t scratch_bytes;
 };
 
-// align: a slice's columns are a multiple of it, so that every slice of an
-// aligned row starts on a 16-byte boundary (4 for 4-byte keys, 8 for 2-byte
-// keys).  min_slice: the columns a slice keeps.  The 16-bit calls share every
-// threshold, in columns, but this one: their sweep
-// (profiles/rows_wide16_plan_sweep.jsonl) puts it at 8192 columns, the same
-// 16 KiB (DESIGN.md "16-bit wide rows").
+// The key width (4 or 2 bytes) sets both.  align: a slice's columns are a
+// multiple of it, so that every slice of an aligned row starts on a 16-byte
+// boundary (4 for 4-byte keys, 8 for 2-byte keys).  min_slice: the columns a
+// slice keeps.  The 16-bit calls share every threshold, in columns, but this
+// one: their sweep (profiles/rows_wide16_plan_sweep.jsonl) puts it at 8192
+// columns, the same 16 KiB (DESIGN.md "16-bit wide rows").
 constexpr int32_t WIDE16_MIN_SLICE = 8192;
-WidePlan wide_plan(int64_t rows, int32_t cols, int num_cu, int32_t force_slices, int32_t force_group,
-                   int32_t align = 4, int32_t min_slice = WIDE_MIN_SLICE) {
+constexpr int32_t wide_align(size_t key_bytes) { return (int32_t)(16 / key_bytes); }
+WidePlan wide_plan(size_t key_bytes, int64_t rows, int32_t cols, int num_cu, int32_t force_slices, int32_t force_group) {
+    const int32_t align = wide_align(key_bytes), min_slice = key_bytes == 2 ? WIDE16_MIN_SLICE : WIDE_MIN_SLICE;
     int64_t want = force_slices;
     if (want <= 0) {
         if (rows <= 0 || rows >= (int64_t)WIDE_FUSED_ROWS_PER_CU * num_cu || cols <= WIDE_FUSED_COLS) {
@@ -957,22 +958,103 @@ WidePlan wide_plan(int64_t rows, int32_t cols, int num_cu, int32_t force_slices,
     return p;
 }
 
-// The split form's scratch for groups of g rows; new buffers are zeroed.
-int reserve_wide(kth_ctx *c, int64_t g) {
-    const u64 had_hist = c->wide_hist.count, had_state = c->wide_state.count;
-    int rc = c->wide_hist.reserve((u64)g * kth::NBINS);
-    if (rc == KTH_OK) rc = c->wide_state.reserve((u64)g);
-    if (rc == KTH_OK) rc = c->wide_cnt.reserve((u64)g * 2 * kth::WD_MAX_SLICES);
-    if (rc != KTH_OK) {
-        release_all(c->wide_hist, c->wide_state, c->wide_cnt);
+bool wide_dims_ok(int64_t rows, int32_t cols) { return rows >= 0 && cols >= 1 && cols <= KTH_WIDE_MAX_COLS; }
+
+// The automatic plan of kth_wide_rows_plan and kth_wide_rows_plan_k16.
+int wide_plan_out(size_t key_bytes, int64_t rows, int32_t cols, int num_cu, int32_t *slices, int32_t *slice_keys,
+                  int32_t *group_rows, int64_t *scratch_bytes) {
+    if (!wide_dims_ok(rows, cols) || num_cu < 1) return KTH_EINVAL;
+    const WidePlan p = wide_plan(key_bytes, rows, cols, num_cu, 0, 0);
+    if (slices) *slices = p.slices;
+    if (slice_keys) *slice_keys = p.slice_keys;
+    if (group_rows) *group_rows = p.group_rows;
+    if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
+    return KTH_OK;
+}
+
+// The shape every wide-rows call checks (its outputs, k and kind are its own).
+bool wide_shape_ok(const kth_ctx *c, const void *d_keys, int64_t rows, int32_t cols, int64_t ld) {
+    return c && d_keys && wide_dims_ok(rows, cols) && ld >= cols;
+}
+
+// The reserve rule of the split forms' scratch.  One buffer of a family: the
+// elements wanted, and whether its sequences need it zero when they start (a
+// sequence that ends leaves it so).
+template <class T>
+struct Scratch {
+    DevBuf<T> &buf;
+    u64 want;
+    bool zeroed;
+    u64 had;
+    Scratch(DevBuf<T> &b, u64 w, bool z) : buf(b), want(w), zeroed(z), had(b.count) {}
+    int zero(kth_ctx *c, bool dirty) const {
+        if (zeroed && (buf.count != had || dirty)) HIP_TRY(hipMemsetAsync(buf.p, 0, buf.count * sizeof(T), c->stream));
+        return KTH_OK;
+    }
+};
+// Every buffer or none; a zeroed one is cleared when it is new or when a
+// sequence of the family was cut short (`dirty`).
+template <class... T>
+int reserve_scratch(kth_ctx *c, bool &dirty, const Scratch<T> &...s) {
+    int rc = KTH_OK;
+    if (!(((rc = s.buf.reserve(s.want)) == KTH_OK) && ...)) {
+        release_all(s.buf...);
         return rc;
     }
-    if (c->wide_hist.count != had_hist || c->wide_dirty)
-        HIP_TRY(hipMemsetAsync(c->wide_hist.p, 0, c->wide_hist.count * sizeof(uint32_t), c->stream));
-    if (c->wide_state.count != had_state || c->wide_dirty)
-        HIP_TRY(hipMemsetAsync(c->wide_state.p, 0, c->wide_state.count * sizeof(kth::WideState), c->stream));
-    c->wide_dirty = false;
+    if (!(((rc = s.zero(c, dirty)) == KTH_OK) && ...)) return rc;
+    dirty = false;
     return KTH_OK;
+}
+
+// The end of a split sequence: one that was cut short has left scratch that is
+// not zero, which the families' next reserve clears.
+template <class... B>
+int sequence_check(B &...dirty) {
+    const int rc = launch_check();
+    if (rc != KTH_OK) ((dirty = true), ...);
+    return rc;
+}
+
+// p + off of an output or a per-row array that may be absent.
+template <class T>
+T *ptr_at(T *p, u64 off) {
+    return p ? p + off : nullptr;
+}
+
+// A wide-rows call once its arguments are checked: the plan for keys of
+// sizeof(E) bytes with the ctx's forced values, the family's group cap and
+// scratch (the split form's alone; the fused form's cap is wide_plan's), then
+// launch(p, vec, the group's keys, r0, g) for each group of g rows from row r0.
+// vec: every row starts on 16 bytes.
+template <class E, class Launch>
+int wide_rows_drive(kth_ctx *c, const E *keys, int64_t rows, int32_t cols, int64_t ld, int64_t group_max,
+                    int (*reserve)(kth_ctx *, int64_t), Launch launch) {
+    WidePlan p = wide_plan(sizeof(E), rows, cols, c->num_cu, c->wide_force_slices, c->wide_force_group);
+    if (p.slices > 1) {
+        p.group_rows = (int32_t)std::min<int64_t>(p.group_rows, group_max);
+        KTH_TRY(reserve(c, p.group_rows));
+    }
+    const bool vec = (reinterpret_cast<uintptr_t>(keys) & 15u) == 0 && ld % wide_align(sizeof(E)) == 0;
+    for (int64_t r0 = 0; r0 < rows; r0 += p.group_rows)
+        KTH_TRY(launch(p, vec, keys + (u64)r0 * (u64)ld, r0, std::min<int64_t>(p.group_rows, rows - r0)));
+    return KTH_OK;
+}
+
+// The split form's scratch for groups of g rows; new buffers are zeroed.
+int reserve_wide(kth_ctx *c, int64_t g) {
+    return reserve_scratch(c, c->wide_dirty, Scratch(c->wide_hist, (u64)g * kth::NBINS, true),
+                           Scratch(c->wide_state, (u64)g, true),
+                           Scratch(c->wide_cnt, (u64)g * 2 * kth::WD_MAX_SLICES, false));
+}
+
+// A uniform kernel, or for the var calls (VAR) its _var twin, which takes the
+// same arguments and then the group's WideVar.
+template <bool VAR, class U, class V, class... A>
+void launch_twin(U *uniform, V *var, dim3 grid, int block, kth_ctx *c, const kth::WideVar &v, A... args) {
+    if constexpr (VAR)
+        var<<<grid, block, 0, c->stream>>>(args..., v);
+    else
+        uniform<<<grid, block, 0, c->stream>>>(args...);
 }
 
 // One group of g rows: the fused launch, or the split form's sequence -- per
@@ -984,75 +1066,52 @@ template <bool F32, bool VEC, bool TOPK, bool VAR>
 int launch_wide_group(kth_ctx *c, const WidePlan &p, const uint32_t *keys, int64_t g, uint32_t cols, u64 ld, uint32_t k,
                       uint32_t flip, uint32_t *out, uint32_t *vals, int32_t *idx, const kth::WideVar &v) {
     if (p.slices == 1) {
-        if constexpr (VAR)
-            kth::k_wide_fused_var<F32, VEC, TOPK><<<(int)g, kth::WD_FBLOCK, 0, c->stream>>>(keys, ld, cols, k, flip, out,
-                                                                                         vals, idx, v);
-        else
-            kth::k_wide_fused<F32, VEC, TOPK><<<(int)g, kth::WD_FBLOCK, 0, c->stream>>>(keys, ld, cols, k, flip, out, vals, idx);
+        launch_twin<VAR>(kth::k_wide_fused<F32, VEC, TOPK>, kth::k_wide_fused_var<F32, VEC, TOPK>, (int)g, kth::WD_FBLOCK, c,
+                         v, keys, ld, cols, k, flip, out, vals, idx);
         return launch_check();
     }
     const dim3 grid((unsigned)p.slices, (unsigned)g);
     const uint32_t sk = (uint32_t)p.slice_keys;
+    uint32_t *hist = c->wide_hist.p, *cnt = c->wide_cnt.p;
+    kth::WideState *state = c->wide_state.p;
     for (int pass = 0; pass < 3; ++pass) {
-        if constexpr (VAR) {
-            kth::k_wide_count_var<F32, VEC><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, flip, pass,
-                                                                                c->wide_hist.p, c->wide_state.p, v);
-            kth::k_wide_pick_var<F32><<<(int)g, kth::WD_BLOCK, 0, c->stream>>>(c->wide_hist.p, c->wide_state.p, pass, cols, k,
-                                                                            flip, TOPK ? nullptr : out, v);
-        } else {
-            kth::k_wide_count<F32, VEC><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, flip, pass, c->wide_hist.p,
-                                                                            c->wide_state.p);
-            kth::k_wide_pick<F32><<<(int)g, kth::WD_BLOCK, 0, c->stream>>>(c->wide_hist.p, c->wide_state.p, pass, cols, k, flip,
-                                                                        TOPK ? nullptr : out);
-        }
+        launch_twin<VAR>(kth::k_wide_count<F32, VEC>, kth::k_wide_count_var<F32, VEC>, grid, kth::WD_BLOCK, c, v, keys, ld,
+                         cols, sk, flip, pass, hist, state);
+        launch_twin<VAR>(kth::k_wide_pick<F32>, kth::k_wide_pick_var<F32>, (int)g, kth::WD_BLOCK, c, v, hist, state, pass,
+                         cols, k, flip, TOPK ? nullptr : out);
     }
-    if constexpr (TOPK && VAR) {
-        kth::k_wide_tk_count_var<F32, VEC><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, flip, c->wide_state.p,
-                                                                               c->wide_cnt.p, v);
-        kth::k_wide_tk_write_var<F32, VEC><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, flip, k, c->wide_state.p,
-                                                                               c->wide_cnt.p, vals, idx, v);
-    } else if constexpr (TOPK) {
-        kth::k_wide_tk_count<F32, VEC><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, flip, c->wide_state.p,
-                                                                           c->wide_cnt.p);
-        kth::k_wide_tk_write<F32, VEC><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, flip, k, c->wide_state.p,
-                                                                           c->wide_cnt.p, vals, idx);
+    if constexpr (TOPK) {
+        launch_twin<VAR>(kth::k_wide_tk_count<F32, VEC>, kth::k_wide_tk_count_var<F32, VEC>, grid, kth::WD_BLOCK, c, v, keys,
+                         ld, cols, sk, flip, state, cnt);
+        launch_twin<VAR>(kth::k_wide_tk_write<F32, VEC>, kth::k_wide_tk_write_var<F32, VEC>, grid, kth::WD_BLOCK, c, v, keys,
+                         ld, cols, sk, flip, k, state, cnt, vals, idx);
     }
-    const int rc = launch_check();
-    if (rc != KTH_OK) c->wide_dirty = true;
-    return rc;
+    return sequence_check(c->wide_dirty);
 }
 
 // A var call's arrays at row r0 (the host loops advance them like the outputs).
 kth::WideVar wide_var_at(const kth::WideVar &v, int64_t r0) {
-    return kth::WideVar{v.lens ? v.lens + r0 : nullptr, v.ks ? v.ks + r0 : nullptr, v.cnt ? v.cnt + r0 : nullptr};
+    return kth::WideVar{ptr_at(v.lens, r0), ptr_at(v.ks, r0), ptr_at(v.cnt, r0)};
 }
 
-// The eight 32-bit wide-rows entry points: the argument check, the plan, the
-// scratch and the loop over row groups.
+// The eight 32-bit wide-rows entry points: the argument check, then the rows.
 template <bool F32, bool TOPK, bool VAR = false>
 int wide_rows_entry(kth_ctx *c, const void *d_keys, int64_t rows, int32_t cols, int64_t ld, int32_t k, void *d_out,
                     int largest = 0, void *d_vals = nullptr, int32_t *d_idx = nullptr,
                     const kth::WideVar &var = kth::WideVar{}) {
     const bool has_out = TOPK ? d_vals || d_idx : d_out != nullptr;
-    if (!c || !d_keys || !has_out || rows < 0 || cols < 1 || cols > KTH_WIDE_MAX_COLS || ld < cols || k < 1 || k > cols)
-        return KTH_EINVAL;
+    if (!wide_shape_ok(c, d_keys, rows, cols, ld) || !has_out || k < 1 || k > cols) return KTH_EINVAL;
     if (rows == 0) return KTH_OK;
     KTH_TRY(set_device(c));
-    const WidePlan p = wide_plan(rows, cols, c->num_cu, c->wide_force_slices, c->wide_force_group);
-    if (p.slices > 1) KTH_TRY(reserve_wide(c, p.group_rows));
-    const uint32_t *keys = static_cast<const uint32_t *>(d_keys);
     uint32_t *out = static_cast<uint32_t *>(d_out), *vals = static_cast<uint32_t *>(d_vals);
-    const bool vec = (reinterpret_cast<uintptr_t>(keys) & 15u) == 0 && ld % 4 == 0;
     const uint32_t flip = TOPK && largest ? 0xFFFFFFFFu : 0u;
-    for (int64_t r0 = 0; r0 < rows; r0 += p.group_rows) {
-        const int64_t g = std::min<int64_t>(p.group_rows, rows - r0);
-        const uint32_t *gk = keys + (u64)r0 * (u64)ld;
-        uint32_t *go = out ? out + r0 : nullptr, *gv = vals ? vals + (u64)r0 * (u64)k : nullptr;
-        int32_t *gi = d_idx ? d_idx + (u64)r0 * (u64)k : nullptr;
-        const auto launch = vec ? launch_wide_group<F32, true, TOPK, VAR> : launch_wide_group<F32, false, TOPK, VAR>;
-        KTH_TRY(launch(c, p, gk, g, (uint32_t)cols, (u64)ld, (uint32_t)k, flip, go, gv, gi, wide_var_at(var, r0)));
-    }
-    return KTH_OK;
+    return wide_rows_drive(
+        c, static_cast<const uint32_t *>(d_keys), rows, cols, ld, WIDE_GROUP_MAX, reserve_wide,
+        [&](const WidePlan &p, bool vec, const uint32_t *gk, int64_t r0, int64_t g) {
+            const auto launch = vec ? launch_wide_group<F32, true, TOPK, VAR> : launch_wide_group<F32, false, TOPK, VAR>;
+            return launch(c, p, gk, g, (uint32_t)cols, (u64)ld, (uint32_t)k, flip, ptr_at(out, r0),
+                          ptr_at(vals, (u64)r0 * (u64)k), ptr_at(d_idx, (u64)r0 * (u64)k), wide_var_at(var, r0));
+        });
 }
 
 // 16-bit wide rows (kth_rows_wide16.hpp): the same plan with slices of a
@@ -1064,91 +1123,56 @@ int launch_wide16_group(kth_ctx *c, const WidePlan &p, const uint16_t *keys, int
                         const kth::WideVar &v) {
     const uint32_t nl2 = kth::k16_nl(kind) * 0x10001u, top2 = kth::k16_top(kind) * 0x10001u;
     if (p.slices == 1) {
-        if constexpr (VAR)
-            kth::k_wide16_fused_var<CV, VEC, TOPK><<<(int)g, kth::WD_FBLOCK, 0, c->stream>>>(keys, ld, cols, k, flip2, nl2,
-                                                                                          top2, kind, out, vals, idx, v);
-        else
-            kth::k_wide16_fused<CV, VEC, TOPK><<<(int)g, kth::WD_FBLOCK, 0, c->stream>>>(keys, ld, cols, k, flip2, nl2, top2,
-                                                                                      kind, out, vals, idx);
+        launch_twin<VAR>(kth::k_wide16_fused<CV, VEC, TOPK>, kth::k_wide16_fused_var<CV, VEC, TOPK>, (int)g, kth::WD_FBLOCK,
+                         c, v, keys, ld, cols, k, flip2, nl2, top2, kind, out, vals, idx);
         return launch_check();
     }
     const dim3 grid((unsigned)p.slices, (unsigned)g);
     const uint32_t sk = (uint32_t)p.slice_keys;
+    uint32_t *hist = c->wide_hist.p, *cnt = c->wide_cnt.p;
+    kth::WideState *state = c->wide_state.p;
     uint16_t *sel_out = TOPK ? nullptr : out;
-    if constexpr (VAR) {
-        kth::k_wide16_count_var<CV, VEC, 0><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, flip2, nl2, top2,
-                                                                                c->wide_hist.p, c->wide_state.p, v);
-        kth::k_wide16_pick_var<<<(int)g, kth::WD_BLOCK, 0, c->stream>>>(c->wide_hist.p, c->wide_state.p, 0, cols, k, flip2,
-                                                                     kind, sel_out, v);
-        kth::k_wide16_count_var<CV, VEC, 1><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, flip2, nl2, top2,
-                                                                                c->wide_hist.p, c->wide_state.p, v);
-        kth::k_wide16_pick_var<<<(int)g, kth::WD_BLOCK, 0, c->stream>>>(c->wide_hist.p, c->wide_state.p, 1, cols, k, flip2,
-                                                                     kind, sel_out, v);
-        if constexpr (TOPK) {
-            kth::k_wide16_tk_count_var<CV, VEC><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, flip2, nl2, top2,
-                                                                                    c->wide_state.p, c->wide_cnt.p, v);
-            kth::k_wide16_tk_write_var<CV, VEC><<<grid, kth::WD_BLOCK, 0, c->stream>>>(
-                keys, ld, cols, sk, flip2, nl2, top2, kind, k, c->wide_state.p, c->wide_cnt.p, vals, idx, v);
-        }
-        const int rc = launch_check();
-        if (rc != KTH_OK) c->wide_dirty = true;
-        return rc;
+    launch_twin<VAR>(kth::k_wide16_count<CV, VEC, 0>, kth::k_wide16_count_var<CV, VEC, 0>, grid, kth::WD_BLOCK, c, v, keys,
+                     ld, cols, sk, flip2, nl2, top2, hist, state);
+    launch_twin<VAR>(kth::k_wide16_pick, kth::k_wide16_pick_var, (int)g, kth::WD_BLOCK, c, v, hist, state, 0, cols, k, flip2,
+                     kind, sel_out);
+    launch_twin<VAR>(kth::k_wide16_count<CV, VEC, 1>, kth::k_wide16_count_var<CV, VEC, 1>, grid, kth::WD_BLOCK, c, v, keys,
+                     ld, cols, sk, flip2, nl2, top2, hist, state);
+    launch_twin<VAR>(kth::k_wide16_pick, kth::k_wide16_pick_var, (int)g, kth::WD_BLOCK, c, v, hist, state, 1, cols, k, flip2,
+                     kind, sel_out);
+    if constexpr (TOPK) {
+        launch_twin<VAR>(kth::k_wide16_tk_count<CV, VEC>, kth::k_wide16_tk_count_var<CV, VEC>, grid, kth::WD_BLOCK, c, v,
+                         keys, ld, cols, sk, flip2, nl2, top2, state, cnt);
+        launch_twin<VAR>(kth::k_wide16_tk_write<CV, VEC>, kth::k_wide16_tk_write_var<CV, VEC>, grid, kth::WD_BLOCK, c, v,
+                         keys, ld, cols, sk, flip2, nl2, top2, kind, k, state, cnt, vals, idx);
     }
-    kth::k_wide16_count<CV, VEC, 0><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, flip2, nl2, top2,
-                                                                        c->wide_hist.p, c->wide_state.p);
-    kth::k_wide16_pick<<<(int)g, kth::WD_BLOCK, 0, c->stream>>>(c->wide_hist.p, c->wide_state.p, 0, cols, k, flip2, kind,
-                                                             sel_out);
-    kth::k_wide16_count<CV, VEC, 1><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, flip2, nl2, top2,
-                                                                        c->wide_hist.p, c->wide_state.p);
-    kth::k_wide16_pick<<<(int)g, kth::WD_BLOCK, 0, c->stream>>>(c->wide_hist.p, c->wide_state.p, 1, cols, k, flip2, kind,
-                                                             sel_out);
-    if (TOPK) {
-        kth::k_wide16_tk_count<CV, VEC><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, flip2, nl2, top2,
-                                                                            c->wide_state.p, c->wide_cnt.p);
-        kth::k_wide16_tk_write<CV, VEC><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, flip2, nl2, top2, kind, k,
-                                                                            c->wide_state.p, c->wide_cnt.p, vals, idx);
-    }
-    const int rc = launch_check();
-    if (rc != KTH_OK) c->wide_dirty = true;
-    return rc;
+    return sequence_check(c->wide_dirty);
 }
 
-template <int CV, bool TOPK, bool VAR>
-int launch_wide16_rows(kth_ctx *c, const WidePlan &p, const uint16_t *keys, int64_t rows, uint32_t cols, u64 ld,
-                       uint32_t k, uint32_t flip2, int kind, uint16_t *out, uint16_t *vals, int32_t *idx,
-                       const kth::WideVar &var) {
-    const bool vec = (reinterpret_cast<uintptr_t>(keys) & 15u) == 0 && ld % 8 == 0;
-    const auto launch = vec ? launch_wide16_group<CV, true, TOPK, VAR> : launch_wide16_group<CV, false, TOPK, VAR>;
-    for (int64_t r0 = 0; r0 < rows; r0 += p.group_rows) {
-        const int64_t g = std::min<int64_t>(p.group_rows, rows - r0);
-        KTH_TRY(launch(c, p, keys + (u64)r0 * ld, g, cols, ld, k, flip2, kind, out ? out + r0 : nullptr,
-                       vals ? vals + (u64)r0 * k : nullptr, idx ? idx + (u64)r0 * k : nullptr, wide_var_at(var, r0)));
-    }
-    return KTH_OK;
-}
-
-// The four 16-bit wide-rows entry points: the argument check, the plan, the
-// scratch and the loop over row groups.
+// The four 16-bit wide-rows entry points: the argument check, then the rows,
+// each group with the launch of the kind's key class and of the load.
 template <bool TOPK, bool VAR = false>
 int wide16_rows_entry(kth_ctx *c, const void *d_keys, int64_t rows, int32_t cols, int64_t ld, int32_t k, int kind,
                       uint16_t *d_out, int largest = 0, uint16_t *d_vals = nullptr, int32_t *d_idx = nullptr,
                       const kth::WideVar &var = kth::WideVar{}) {
     const bool has_out = TOPK ? d_vals || d_idx : d_out != nullptr;
-    if (!c || !d_keys || !has_out || rows < 0 || cols < 1 || cols > KTH_WIDE_MAX_COLS || ld < cols || k < 1 || k > cols ||
-        kind < KTH_K16_I16 || kind > KTH_K16_BF16)
+    if (!wide_shape_ok(c, d_keys, rows, cols, ld) || !has_out || k < 1 || k > cols || kind < KTH_K16_I16 ||
+        kind > KTH_K16_BF16)
         return KTH_EINVAL;
     if (rows == 0) return KTH_OK;
     KTH_TRY(set_device(c));
-    const WidePlan p = wide_plan(rows, cols, c->num_cu, c->wide_force_slices, c->wide_force_group, 8, WIDE16_MIN_SLICE);
-    if (p.slices > 1) KTH_TRY(reserve_wide(c, p.group_rows));
-    const uint16_t *keys = static_cast<const uint16_t *>(d_keys);
     const uint32_t flip2 = TOPK && largest ? 0xFFFFFFFFu : 0u;
-    const uint32_t C = (uint32_t)cols, K = (uint32_t)k;
-    if (kth::k16_float(kind))
-        return launch_wide16_rows<2, TOPK, VAR>(c, p, keys, rows, C, (u64)ld, K, flip2, kind, d_out, d_vals, d_idx, var);
-    if (kind == KTH_K16_I16)
-        return launch_wide16_rows<1, TOPK, VAR>(c, p, keys, rows, C, (u64)ld, K, flip2, kind, d_out, d_vals, d_idx, var);
-    return launch_wide16_rows<0, TOPK, VAR>(c, p, keys, rows, C, (u64)ld, K, flip2, kind, d_out, d_vals, d_idx, var);
+    const int cv = kth::k16_float(kind) ? 2 : kind == KTH_K16_I16 ? 1 : 0;
+    static constexpr decltype(&launch_wide16_group<0, false, TOPK, VAR>) launch[3][2] = {  // [CV][VEC]
+        {launch_wide16_group<0, false, TOPK, VAR>, launch_wide16_group<0, true, TOPK, VAR>},
+        {launch_wide16_group<1, false, TOPK, VAR>, launch_wide16_group<1, true, TOPK, VAR>},
+        {launch_wide16_group<2, false, TOPK, VAR>, launch_wide16_group<2, true, TOPK, VAR>}};
+    return wide_rows_drive(c, static_cast<const uint16_t *>(d_keys), rows, cols, ld, WIDE_GROUP_MAX, reserve_wide,
+                           [&](const WidePlan &p, bool vec, const uint16_t *gk, int64_t r0, int64_t g) {
+                               return launch[cv][vec](c, p, gk, g, (uint32_t)cols, (u64)ld, (uint32_t)k, flip2, kind,
+                                                      ptr_at(d_out, r0), ptr_at(d_vals, (u64)r0 * (u64)k),
+                                                      ptr_at(d_idx, (u64)r0 * (u64)k), wide_var_at(var, r0));
+                           });
 }
 
 // Top-p rows (kth_rows_topp.hpp).  The wide-rows plan; the split form's scratch
@@ -1159,22 +1183,25 @@ constexpr int64_t TP_GROUP_MAX = WIDE_SCRATCH_MAX / TP_ROW_BYTES;  // 1362 rows
 
 // The split form's scratch for groups of g rows; new buffers are zeroed.
 int reserve_topp(kth_ctx *c, int64_t g) {
-    const u64 had_mass = c->tp_mass.count, had_cnt = c->tp_cnt.count, had_state = c->tp_state.count;
-    int rc = c->tp_mass.reserve((u64)g * kth::NBINS);
-    if (rc == KTH_OK) rc = c->tp_cnt.reserve((u64)g * kth::NBINS);
-    if (rc == KTH_OK) rc = c->tp_state.reserve((u64)g);
-    if (rc != KTH_OK) {
-        release_all(c->tp_mass, c->tp_cnt, c->tp_state);
-        return rc;
-    }
-    if (c->tp_mass.count != had_mass || c->tp_dirty)
-        HIP_TRY(hipMemsetAsync(c->tp_mass.p, 0, c->tp_mass.count * sizeof(u64), c->stream));
-    if (c->tp_cnt.count != had_cnt || c->tp_dirty)
-        HIP_TRY(hipMemsetAsync(c->tp_cnt.p, 0, c->tp_cnt.count * sizeof(uint32_t), c->stream));
-    if (c->tp_state.count != had_state || c->tp_dirty)
-        HIP_TRY(hipMemsetAsync(c->tp_state.p, 0, c->tp_state.count * sizeof(kth::TpState), c->stream));
-    c->tp_dirty = false;
-    return KTH_OK;
+    return reserve_scratch(c, c->tp_dirty, Scratch(c->tp_mass, (u64)g * kth::NBINS, true),
+                           Scratch(c->tp_cnt, (u64)g * kth::NBINS, true), Scratch(c->tp_state, (u64)g, true));
+}
+
+// A top-p or sampling call's arrays at row r0 (wide_var_at's counterpart).
+kth::TopP topp_at(const kth::TopP &v, int64_t r0) {
+    return kth::TopP{ptr_at(v.lens, r0), ptr_at(v.ps, r0), ptr_at(v.temps, r0), ptr_at(v.ks, r0), v.p, v.temp, v.k};
+}
+// Those calls' check of kind (a KTH_K16_* float kind, or -1 for float32 keys),
+// of temp and of the p that stands in for an absent d_ps.
+bool topp_args_ok(int kind, const float *d_ps, float p, float temp) {
+    return (kind == -1 || kind == KTH_K16_F16 || kind == KTH_K16_BF16) && temp > 0.0f && std::isfinite(temp) &&
+           (d_ps || !std::isnan(p));
+}
+// f(K{}) for the key traits K of `kind`.
+template <class F>
+int topp_dispatch(int kind, F f) {
+    if (kind == -1) return f(kth::TpF32{});
+    return kind == KTH_K16_BF16 ? f(kth::TpK16<true>{}) : f(kth::TpK16<false>{});
 }
 
 // One group of g rows: the fused launch, or the split form's sequence -- pass M,
@@ -1196,36 +1223,23 @@ int launch_topp_group(kth_ctx *c, const WidePlan &p, const typename K::elem *key
         kth::k_tp_pick<K><<<(int)g, kth::WD_BLOCK, 0, c->stream>>>(c->tp_mass.p, c->tp_cnt.p, c->tp_state.p, pass, cols, v,
                                                                  d_n, d_thr, rank);
     }
-    const int rc = launch_check();
-    if (rc != KTH_OK) c->tp_dirty = true;
-    return rc;
+    return sequence_check(c->tp_dirty);
 }
 
-// The nucleus of every row: plan, scratch and the loop over row groups.  The
-// arguments have been checked.  rank (kth_topp_*): rows int32, min(n_r, cap_r).
+// The nucleus of every row.  The arguments have been checked.  rank
+// (kth_topp_*): rows int32, min(n_r, cap_r).
 template <class K>
-int topp_rows(kth_ctx *c, const typename K::elem *keys, int64_t rows, int32_t cols, int64_t ld, const kth::TopP &var,
-              int32_t *d_n, typename K::elem *d_thr, int32_t *rank) {
-    constexpr int32_t align = K::PER;  // 4 columns of 4-byte keys, 8 of 2-byte keys: 16 bytes
-    WidePlan p = wide_plan(rows, cols, c->num_cu, c->wide_force_slices, c->wide_force_group, align,
-                           align == 8 ? WIDE16_MIN_SLICE : WIDE_MIN_SLICE);
-    if (p.slices > 1) {
-        p.group_rows = (int32_t)std::min<int64_t>(p.group_rows, TP_GROUP_MAX);
-        KTH_TRY(reserve_topp(c, p.group_rows));
-    }
-    const bool vec = (reinterpret_cast<uintptr_t>(keys) & 15u) == 0 && ld % align == 0;
-    const auto launch = vec ? launch_topp_group<K, true> : launch_topp_group<K, false>;
-    for (int64_t r0 = 0; r0 < rows; r0 += p.group_rows) {
-        const int64_t g = std::min<int64_t>(p.group_rows, rows - r0);
-        kth::TopP v = var;
-        if (v.lens) v.lens += r0;
-        if (v.ps) v.ps += r0;
-        if (v.temps) v.temps += r0;
-        if (v.ks) v.ks += r0;
-        KTH_TRY(launch(c, p, keys + (u64)r0 * (u64)ld, g, (uint32_t)cols, (u64)ld, v, d_n ? d_n + r0 : nullptr,
-                       d_thr ? d_thr + r0 : nullptr, rank ? rank + r0 : nullptr));
-    }
-    return KTH_OK;
+int topp_rows(kth_ctx *c, const void *d_keys, int64_t rows, int32_t cols, int64_t ld, const kth::TopP &var, int32_t *d_n,
+              void *d_thr, int32_t *rank) {
+    using E = typename K::elem;
+    static_assert(K::PER == wide_align(sizeof(E)), "a load of K::PER columns is the 16 bytes of the plan's alignment");
+    E *thr = static_cast<E *>(d_thr);
+    return wide_rows_drive(c, static_cast<const E *>(d_keys), rows, cols, ld, TP_GROUP_MAX, reserve_topp,
+                           [&](const WidePlan &p, bool vec, const E *gk, int64_t r0, int64_t g) {
+                               const auto launch = vec ? launch_topp_group<K, true> : launch_topp_group<K, false>;
+                               return launch(c, p, gk, g, (uint32_t)cols, (u64)ld, topp_at(var, r0), ptr_at(d_n, r0),
+                                             ptr_at(thr, r0), ptr_at(rank, r0));
+                           });
 }
 
 // The four top-p entry points: the argument check, then the nucleus and, for
@@ -1236,10 +1250,8 @@ int topp_entry(kth_ctx *c, const void *d_keys, int64_t rows, int32_t cols, int64
                const int32_t *d_ks, int32_t k, const float *d_ps, float p, const float *d_temps, float temp, int kind,
                int32_t *d_n, void *d_thr, void *d_vals, int32_t *d_idx, int32_t *d_cnt) {
     const bool has_out = TOPK ? d_vals || d_idx : d_n || d_thr;
-    if (!c || !d_keys || !has_out || rows < 0 || cols < 1 || cols > KTH_WIDE_MAX_COLS || ld < cols) return KTH_EINVAL;
+    if (!wide_shape_ok(c, d_keys, rows, cols, ld) || !has_out || !topp_args_ok(kind, d_ps, p, temp)) return KTH_EINVAL;
     if (TOPK && (k < 1 || k > cols)) return KTH_EINVAL;
-    if (kind != -1 && kind != KTH_K16_F16 && kind != KTH_K16_BF16) return KTH_EINVAL;
-    if (!(temp > 0.0f) || !std::isfinite(temp) || (!d_ps && std::isnan(p))) return KTH_EINVAL;
     if (rows == 0) return KTH_OK;
     KTH_TRY(set_device(c));
     int32_t *rank = nullptr;
@@ -1248,24 +1260,13 @@ int topp_entry(kth_ctx *c, const void *d_keys, int64_t rows, int32_t cols, int64
         rank = c->tp_rank.p;
     }
     const kth::TopP var{d_lens, d_ps, d_temps, TOPK ? d_ks : nullptr, p, temp, TOPK ? k : 0};
-    if (kind == -1) {
-        KTH_TRY(topp_rows<kth::TpF32>(c, static_cast<const uint32_t *>(d_keys), rows, cols, ld, var, d_n,
-                                      static_cast<uint32_t *>(d_thr), rank));
-        if (TOPK)
-            return wide_rows_entry<true, true, true>(c, d_keys, rows, cols, ld, k, nullptr, 1, d_vals, d_idx,
-                                                     kth::WideVar{d_lens, rank, d_cnt});
-        return KTH_OK;
-    }
-    const uint16_t *keys = static_cast<const uint16_t *>(d_keys);
-    uint16_t *thr = static_cast<uint16_t *>(d_thr);
-    if (kind == KTH_K16_BF16)
-        KTH_TRY(topp_rows<kth::TpK16<true>>(c, keys, rows, cols, ld, var, d_n, thr, rank));
-    else
-        KTH_TRY(topp_rows<kth::TpK16<false>>(c, keys, rows, cols, ld, var, d_n, thr, rank));
-    if (TOPK)
-        return wide16_rows_entry<true, true>(c, d_keys, rows, cols, ld, k, kind, nullptr, 1,
-                                             static_cast<uint16_t *>(d_vals), d_idx, kth::WideVar{d_lens, rank, d_cnt});
-    return KTH_OK;
+    KTH_TRY(topp_dispatch(
+        kind, [&](auto K) { return topp_rows<decltype(K)>(c, d_keys, rows, cols, ld, var, d_n, d_thr, rank); }));
+    if (!TOPK) return KTH_OK;
+    const kth::WideVar ranks{d_lens, rank, d_cnt};
+    if (kind == -1) return wide_rows_entry<true, true, true>(c, d_keys, rows, cols, ld, k, nullptr, 1, d_vals, d_idx, ranks);
+    return wide16_rows_entry<true, true>(c, d_keys, rows, cols, ld, k, kind, nullptr, 1, static_cast<uint16_t *>(d_vals),
+                                         d_idx, ranks);
 }
 
 // Sampling rows (kth_rows_sample.hpp).  The wide-rows plan; the split form adds a
@@ -1277,17 +1278,8 @@ constexpr int64_t SM_GROUP_MAX = WIDE_SCRATCH_MAX / SM_ROW_BYTES;  // 1305 rows
 // The split form's scratch for groups of g rows; a new state buffer is zeroed.
 int reserve_sample(kth_ctx *c, int64_t g) {
     KTH_TRY(reserve_topp(c, g));
-    const u64 had_state = c->sm_state.count;
-    int rc = c->sm_state.reserve((u64)g);
-    if (rc == KTH_OK) rc = c->sm_loc.reserve((u64)g * kth::WD_MAX_SLICES);
-    if (rc != KTH_OK) {
-        release_all(c->sm_state, c->sm_loc);
-        return rc;
-    }
-    if (c->sm_state.count != had_state || c->sm_dirty)
-        HIP_TRY(hipMemsetAsync(c->sm_state.p, 0, c->sm_state.count * sizeof(kth::SmState), c->stream));
-    c->sm_dirty = false;
-    return KTH_OK;
+    return reserve_scratch(c, c->sm_dirty, Scratch(c->sm_state, (u64)g, true),
+                           Scratch(c->sm_loc, (u64)g * kth::WD_MAX_SLICES, false));
 }
 
 // One group of g rows: the fused launch, or the split form's sequence -- pass M,
@@ -1314,36 +1306,20 @@ int launch_sample_group(kth_ctx *c, const WidePlan &p, const typename K::elem *k
     kth::k_sm_loc_count<K, VEC><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, c->sm_state.p, c->sm_loc.p, v);
     kth::k_sm_loc_pick<K, VEC><<<grid, kth::WD_BLOCK, 0, c->stream>>>(keys, ld, cols, sk, c->sm_state.p, c->sm_loc.p, v,
                                                                    d_tok, d_cnt);
-    const int rc = launch_check();
-    if (rc != KTH_OK) c->tp_dirty = c->sm_dirty = true;
-    return rc;
+    return sequence_check(c->tp_dirty, c->sm_dirty);
 }
 
-// One token of every row: plan, scratch and the loop over row groups.  The
-// arguments have been checked.
+// One token of every row.  The arguments have been checked.
 template <class K>
-int sample_rows(kth_ctx *c, const typename K::elem *keys, int64_t rows, int32_t cols, int64_t ld, const kth::TopP &var,
-                bool no_a, const float *d_us, int32_t *d_tok, int32_t *d_cnt) {
-    constexpr int32_t align = K::PER;
-    WidePlan p = wide_plan(rows, cols, c->num_cu, c->wide_force_slices, c->wide_force_group, align,
-                           align == 8 ? WIDE16_MIN_SLICE : WIDE_MIN_SLICE);
-    if (p.slices > 1) {
-        p.group_rows = (int32_t)std::min<int64_t>(p.group_rows, SM_GROUP_MAX);
-        KTH_TRY(reserve_sample(c, p.group_rows));
-    }
-    const bool vec = (reinterpret_cast<uintptr_t>(keys) & 15u) == 0 && ld % align == 0;
-    const auto launch = vec ? launch_sample_group<K, true> : launch_sample_group<K, false>;
-    for (int64_t r0 = 0; r0 < rows; r0 += p.group_rows) {
-        const int64_t g = std::min<int64_t>(p.group_rows, rows - r0);
-        kth::TopP v = var;
-        if (v.lens) v.lens += r0;
-        if (v.ps) v.ps += r0;
-        if (v.temps) v.temps += r0;
-        if (v.ks) v.ks += r0;
-        KTH_TRY(launch(c, p, keys + (u64)r0 * (u64)ld, g, (uint32_t)cols, (u64)ld, v, no_a, d_us + r0, d_tok + r0,
-                       d_cnt ? d_cnt + r0 : nullptr));
-    }
-    return KTH_OK;
+int sample_rows(kth_ctx *c, const void *d_keys, int64_t rows, int32_t cols, int64_t ld, const kth::TopP &var, bool no_a,
+                const float *d_us, int32_t *d_tok, int32_t *d_cnt) {
+    using E = typename K::elem;
+    return wide_rows_drive(c, static_cast<const E *>(d_keys), rows, cols, ld, SM_GROUP_MAX, reserve_sample,
+                           [&](const WidePlan &p, bool vec, const E *gk, int64_t r0, int64_t g) {
+                               const auto launch = vec ? launch_sample_group<K, true> : launch_sample_group<K, false>;
+                               return launch(c, p, gk, g, (uint32_t)cols, (u64)ld, topp_at(var, r0), no_a, d_us + r0,
+                                             d_tok + r0, ptr_at(d_cnt, r0));
+                           });
 }
 
 // The two sample entry points: the argument check, then the rows.  kind: a
@@ -1351,20 +1327,14 @@ int sample_rows(kth_ctx *c, const typename K::elem *keys, int64_t rows, int32_t 
 int sample_entry(kth_ctx *c, const void *d_keys, int64_t rows, int32_t cols, int64_t ld, const int32_t *d_lens,
                  const int32_t *d_ks, int32_t k, const float *d_ps, float p, const float *d_temps, float temp,
                  const float *d_us, int kind, int32_t *d_tok, int32_t *d_cnt) {
-    if (!c || !d_keys || !d_us || !d_tok || rows < 0 || cols < 1 || cols > KTH_WIDE_MAX_COLS || ld < cols)
+    if (!wide_shape_ok(c, d_keys, rows, cols, ld) || !d_us || !d_tok || !topp_args_ok(kind, d_ps, p, temp))
         return KTH_EINVAL;
-    if (kind != -1 && kind != KTH_K16_F16 && kind != KTH_K16_BF16) return KTH_EINVAL;
-    if (!(temp > 0.0f) || !std::isfinite(temp) || (!d_ps && std::isnan(p))) return KTH_EINVAL;
     if (rows == 0) return KTH_OK;
     KTH_TRY(set_device(c));
     const kth::TopP var{d_lens, d_ps, d_temps, d_ks, p, temp, k};
     const bool no_a = !d_ps && p >= 1.0f && !d_ks && k <= 0;
-    if (kind == -1)
-        return sample_rows<kth::TpF32>(c, static_cast<const uint32_t *>(d_keys), rows, cols, ld, var, no_a, d_us, d_tok,
-                                       d_cnt);
-    const uint16_t *keys = static_cast<const uint16_t *>(d_keys);
-    if (kind == KTH_K16_BF16) return sample_rows<kth::TpK16<true>>(c, keys, rows, cols, ld, var, no_a, d_us, d_tok, d_cnt);
-    return sample_rows<kth::TpK16<false>>(c, keys, rows, cols, ld, var, no_a, d_us, d_tok, d_cnt);
+    return topp_dispatch(
+        kind, [&](auto K) { return sample_rows<decltype(K)>(c, d_keys, rows, cols, ld, var, no_a, d_us, d_tok, d_cnt); });
 }
 
 // ------------------------------------------------------- ctx creation, in parts
@@ -2418,7 +2388,7 @@ int kth_topk_wide_rows_f32(kth_ctx *c, const float *d_keys, int64_t rows, int32_
 }
 
 int kth_ctx_reserve_wide_rows(kth_ctx *c, int64_t rows, int32_t cols) {
-    if (!c || rows < 0 || cols < 1 || cols > KTH_WIDE_MAX_COLS) return KTH_EINVAL;
+    if (!c || !wide_dims_ok(rows, cols)) return KTH_EINVAL;
     KTH_TRY(set_device(c));
     // for the split form whatever the plan of (rows, cols) is: a forced plan then fits too
     return reserve_wide(c, std::min(std::max<int64_t>(rows, 1), WIDE_GROUP_MAX));
@@ -2426,13 +2396,7 @@ int kth_ctx_reserve_wide_rows(kth_ctx *c, int64_t rows, int32_t cols) {
 
 int kth_wide_rows_plan(int64_t rows, int32_t cols, int num_cu, int32_t *slices, int32_t *slice_keys,
                        int32_t *group_rows, int64_t *scratch_bytes) {
-    if (rows < 0 || cols < 1 || cols > KTH_WIDE_MAX_COLS || num_cu < 1) return KTH_EINVAL;
-    const WidePlan p = wide_plan(rows, cols, num_cu, 0, 0);
-    if (slices) *slices = p.slices;
-    if (slice_keys) *slice_keys = p.slice_keys;
-    if (group_rows) *group_rows = p.group_rows;
-    if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
-    return KTH_OK;
+    return wide_plan_out(4, rows, cols, num_cu, slices, slice_keys, group_rows, scratch_bytes);
 }
 
 int kth_ctx_wide_rows_force(kth_ctx *c, int32_t slices, int32_t group_rows) {
@@ -2454,13 +2418,7 @@ int kth_topk_wide_rows_k16(kth_ctx *c, const void *d_keys, int64_t rows, int32_t
 
 int kth_wide_rows_plan_k16(int64_t rows, int32_t cols, int num_cu, int32_t *slices, int32_t *slice_keys,
                            int32_t *group_rows, int64_t *scratch_bytes) {
-    if (rows < 0 || cols < 1 || cols > KTH_WIDE_MAX_COLS || num_cu < 1) return KTH_EINVAL;
-    const WidePlan p = wide_plan(rows, cols, num_cu, 0, 0, 8, WIDE16_MIN_SLICE);
-    if (slices) *slices = p.slices;
-    if (slice_keys) *slice_keys = p.slice_keys;
-    if (group_rows) *group_rows = p.group_rows;
-    if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
-    return KTH_OK;
+    return wide_plan_out(2, rows, cols, num_cu, slices, slice_keys, group_rows, scratch_bytes);
 }
 
 int kth_select_wide_rows_var_i32(kth_ctx *c, const int32_t *d_keys, int64_t rows, int32_t cols, int64_t ld,
@@ -2534,7 +2492,7 @@ int kth_topp_wide_rows_k16(kth_ctx *c, const void *d_keys, int64_t rows, int32_t
 }
 
 int kth_ctx_reserve_topp_rows(kth_ctx *c, int64_t rows, int32_t cols) {
-    if (!c || rows < 0 || cols < 1 || cols > KTH_WIDE_MAX_COLS) return KTH_EINVAL;
+    if (!c || !wide_dims_ok(rows, cols)) return KTH_EINVAL;
     KTH_TRY(set_device(c));
     // the split form of both sequences whatever the plan of (rows, cols) is: a forced plan then fits too
     KTH_TRY(reserve_topp(c, std::min(std::max<int64_t>(rows, 1), TP_GROUP_MAX)));
@@ -2557,7 +2515,7 @@ int kth_sample_wide_rows_k16(kth_ctx *c, const void *d_keys, int64_t rows, int32
 }
 
 int kth_ctx_reserve_sample_rows(kth_ctx *c, int64_t rows, int32_t cols) {
-    if (!c || rows < 0 || cols < 1 || cols > KTH_WIDE_MAX_COLS) return KTH_EINVAL;
+    if (!c || !wide_dims_ok(rows, cols)) return KTH_EINVAL;
     KTH_TRY(set_device(c));
     // the split form whatever the plan of (rows, cols) is: a forced plan then fits too
     return reserve_sample(c, std::min(std::max<int64_t>(rows, 1), SM_GROUP_MAX));

@@ -31,8 +31,9 @@ ROWS = V.ROWS
 NAN = float("nan")
 PS = (-1.0, 0.0, 0.3, 0.9, 0.999, 1.0, 2.0, NAN)
 TEMPS = (0.5, 1.0, 2.0, 0.0, NAN)
-# (slices, group_rows): fused, three split plans, groups of 3 rows under the automatic plan
-PLANS = ((1, 0), (4, 0), (7, 0), (256, 0), (0, 3))
+# (slices, group_rows): fused, three split plans, groups of 3 rows under the automatic plan and,
+# split in 4, with every per-row array advanced and the scratch reused from group to group
+PLANS = ((1, 0), (4, 0), (7, 0), (256, 0), (0, 3), (4, 3))
 
 
 def eps_of(cols):
