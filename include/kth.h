@@ -348,7 +348,9 @@ int kth_select_rows_f32(kth_ctx *ctx, const float *d_keys, int64_t rows, int32_t
  * ones by column.  d_vals: rows x k values, d_idx: rows x k int32 columns;
  * either may be NULL (not both).  1 <= k <= cols <= KTH_TOPK_MAX_COLS.  Same
  * orders as kth_select_rows_* (float: IEEE total order, NaN above +inf, so
- * NaNs come last for smallest and first for largest). */
+ * NaNs come last for smallest and first for largest).  A value in d_vals has
+ * the bit pattern of an input element; kth_topk_rows_f32 writes a NaN in
+ * d_vals as the canonical quiet NaN 0x7FC00000. */
 #define KTH_TOPK_MAX_COLS 4096
 int kth_topk_rows_i32(kth_ctx *ctx, const int32_t *d_keys, int64_t rows, int32_t cols, int32_t k, int largest,
                       int32_t *d_vals, int32_t *d_idx);
