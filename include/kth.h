@@ -785,6 +785,51 @@ int kth_sample_wide_rows_k16(kth_ctx *ctx, const void *d_keys, int64_t rows, int
                              int32_t *d_cnt);
 int kth_ctx_reserve_sample_rows(kth_ctx *ctx, int64_t rows, int32_t cols);
 
+/* --- rows, sorted top-k: each row of a rows x k top-k output, best first ---------
+ * Every per-row top-k above (kth_topk_rows_*, kth_topk_rows_k16, the wide and
+ * ragged wide calls, kth_topp_wide_rows_*) writes its k keys in column order.
+ * These calls put such an output in the order torch.topk(sorted=True) gives: a
+ * stable sort, in place, of each row's values with their indices.
+ *
+ * Row.  Row r is d_vals[r*k .. r*k + k) and, when d_idx is given, d_idx[r*k ..
+ * r*k + k).  Only its first n_r entries take part: n_r = clamp(d_cnt[r], 0, k),
+ * or k when d_cnt is NULL (d_cnt: `rows` int32 on the device, read when the
+ * launch runs, so a graph replay sees its current contents -- the d_cnt the
+ * ragged and top-p calls write).  Entries [n_r, k), the ragged calls' padding,
+ * are neither read nor written.
+ * Order.  After the call the n_r entries stand best first: ascending in the
+ * order key when largest == 0, descending when largest != 0.  The order key is
+ * the signed order for int32, kth_f32_order_key for float32 (-0.0 < +0.0,
+ * subnormals distinct, every NaN equal to every other NaN and above +inf) and
+ * kth_k16_order_key(bits, kind) for the 16-bit kinds.
+ * Ties.  The sort is stable: entries of equal order key keep their input order,
+ * in either direction.  The top-k calls write in column order, so on their
+ * output ties stand by ascending column, the tie rule of the whole library; the
+ * same definition holds for d_idx == NULL and for any other payload.
+ * Moves.  Values and indices are moved bit for bit: a NaN keeps its payload, and
+ * d_idx is an opaque int32 payload that is never interpreted.  A row with n_r
+ * <= 1 is not stored to at all.
+ *
+ * 1 <= k <= KTH_SORT_MAX_K.  One launch: k <= 64 packs 64 / k' rows into a
+ * wavefront (k' the power of two at or above k) and exchanges across lanes;
+ * larger k sorts a row a workgroup in LDS.  Asynchronous on the ctx stream,
+ * device memory only, no host synchronisation, no allocation, no scratch, no
+ * atomics; graph-capturable under the conditions written at
+ * kth_select_i32_async.  No ctx buffer and not the last-call word is touched:
+ * kth_ctx_last_stats is unaffected, and these calls may alternate with every
+ * other call on one ctx.
+ * KTH_EINVAL before any device work, outputs untouched: a NULL ctx or d_vals,
+ * rows < 0, k < 1, k > KTH_SORT_MAX_K, a bad kind.  d_idx and d_cnt may be
+ * NULL.  rows == 0 returns KTH_OK and launches nothing.  KTH_ENODEV without a
+ * GPU.  (csrc/kth_rows_sort.hpp.) */
+#define KTH_SORT_MAX_K 4096
+int kth_sort_topk_rows_i32(kth_ctx *ctx, int32_t *d_vals, int32_t *d_idx, int64_t rows, int32_t k,
+                           const int32_t *d_cnt, int largest);
+int kth_sort_topk_rows_f32(kth_ctx *ctx, float *d_vals, int32_t *d_idx, int64_t rows, int32_t k,
+                           const int32_t *d_cnt, int largest);
+int kth_sort_topk_rows_k16(kth_ctx *ctx, uint16_t *d_vals, int32_t *d_idx, int64_t rows, int32_t k,
+                           const int32_t *d_cnt, int largest, int kind);
+
 /* --- sharded selection, one process per GPU (TODO-kth-problem-cgm.c:76-278) --
  * The CGM rounds (local median :125-131, Gather :135-136, weighted median
  * :139-165, Bcast :168, 3-way count :171-185, Allreduce :190, discard

@@ -1337,6 +1337,53 @@ int sample_entry(kth_ctx *c, const void *d_keys, int64_t rows, int32_t cols, int
         kind, [&](auto K) { return sample_rows<decltype(K)>(c, d_keys, rows, cols, ld, var, no_a, d_us, d_tok, d_cnt); });
 }
 
+// Sorted top-k rows (kth_rows_sort.hpp): the form by k' = the power of two at
+// or above k, the wave form's grid by its packing (64 / k' rows a wavefront,
+// four wavefronts a workgroup), both bounded -- the kernels stride over rows.
+static_assert(KTH_SORT_MAX_K == kth::SORT_MAX_K, "include/kth.h sorted top-k limit");
+template <class T, int KP>
+void launch_sort_wave(kth_ctx *c, typename T::elem *vals, int32_t *idx, int64_t rows, int32_t k, const int32_t *cnt,
+                      uint32_t flip, int kind) {
+    const int64_t rows_per_wg = (int64_t)(kth::WAVE / KP) * (kth::SORT_BLOCK / kth::WAVE);
+    const int g = (int)std::min<int64_t>((rows + rows_per_wg - 1) / rows_per_wg, kth::SORT_GRID_MAX);
+    kth::k_sort_wave<T, KP><<<g, kth::SORT_BLOCK, 0, c->stream>>>(vals, idx, (u64)rows, (uint32_t)k, cnt, flip, kind);
+}
+
+template <class T>
+int launch_sort(kth_ctx *c, void *d_vals, int32_t *idx, int64_t rows, int32_t k, const int32_t *cnt, uint32_t flip,
+                int kind) {
+    typename T::elem *vals = static_cast<typename T::elem *>(d_vals);
+    int kp = 2;
+    while (kp < k) kp <<= 1;
+    switch (kp) {
+    case 2: launch_sort_wave<T, 2>(c, vals, idx, rows, k, cnt, flip, kind); break;
+    case 4: launch_sort_wave<T, 4>(c, vals, idx, rows, k, cnt, flip, kind); break;
+    case 8: launch_sort_wave<T, 8>(c, vals, idx, rows, k, cnt, flip, kind); break;
+    case 16: launch_sort_wave<T, 16>(c, vals, idx, rows, k, cnt, flip, kind); break;
+    case 32: launch_sort_wave<T, 32>(c, vals, idx, rows, k, cnt, flip, kind); break;
+    case 64: launch_sort_wave<T, 64>(c, vals, idx, rows, k, cnt, flip, kind); break;
+    default: {
+        const int g = (int)std::min<int64_t>(rows, kth::SORT_GRID_MAX);
+        kth::k_sort_wg<T><<<g, kth::SORT_BLOCK, (size_t)kp * sizeof(typename T::comp), c->stream>>>(
+            vals, idx, (u64)rows, (uint32_t)k, cnt, flip, kind);
+    }
+    }
+    return launch_check();
+}
+
+// The three sort entry points: the argument check, then the one launch.  kind:
+// a KTH_K16_* value, -1 for float32 keys, -2 for int32 keys.  A row of one
+// entry is sorted as it stands: k == 1 launches nothing.
+int sort_entry(kth_ctx *c, void *d_vals, int32_t *d_idx, int64_t rows, int32_t k, const int32_t *d_cnt, int largest,
+               int kind) {
+    if (!c || !d_vals || rows < 0 || k < 1 || k > KTH_SORT_MAX_K || kind < -2 || kind > KTH_K16_BF16) return KTH_EINVAL;
+    if (rows == 0 || k == 1) return KTH_OK;
+    KTH_TRY(set_device(c));
+    if (kind == -2) return launch_sort<kth::SortI32>(c, d_vals, d_idx, rows, k, d_cnt, largest ? 0xFFFFFFFFu : 0u, kind);
+    if (kind == -1) return launch_sort<kth::SortF32>(c, d_vals, d_idx, rows, k, d_cnt, largest ? 0xFFFFFFFFu : 0u, kind);
+    return launch_sort<kth::SortK16>(c, d_vals, d_idx, rows, k, d_cnt, largest ? 0xFFFFu : 0u, kind);
+}
+
 // ------------------------------------------------------- ctx creation, in parts
 // Every tuning variable of a ctx (design exploration and A/B runs; unset: the
 // defaults in kth_ctx).  Needs c->num_cu.  Read elsewhere: KTH_STAMPS (the
@@ -2519,6 +2566,22 @@ int kth_ctx_reserve_sample_rows(kth_ctx *c, int64_t rows, int32_t cols) {
     KTH_TRY(set_device(c));
     // the split form whatever the plan of (rows, cols) is: a forced plan then fits too
     return reserve_sample(c, std::min(std::max<int64_t>(rows, 1), SM_GROUP_MAX));
+}
+
+int kth_sort_topk_rows_i32(kth_ctx *c, int32_t *d_vals, int32_t *d_idx, int64_t rows, int32_t k, const int32_t *d_cnt,
+                           int largest) {
+    return sort_entry(c, d_vals, d_idx, rows, k, d_cnt, largest, -2);
+}
+
+int kth_sort_topk_rows_f32(kth_ctx *c, float *d_vals, int32_t *d_idx, int64_t rows, int32_t k, const int32_t *d_cnt,
+                           int largest) {
+    return sort_entry(c, d_vals, d_idx, rows, k, d_cnt, largest, -1);
+}
+
+int kth_sort_topk_rows_k16(kth_ctx *c, uint16_t *d_vals, int32_t *d_idx, int64_t rows, int32_t k, const int32_t *d_cnt,
+                           int largest, int kind) {
+    if (kind < KTH_K16_I16 || kind > KTH_K16_BF16) return KTH_EINVAL;
+    return sort_entry(c, d_vals, d_idx, rows, k, d_cnt, largest, kind);
 }
 
 }  // extern "C"

@@ -2048,3 +2048,4 @@ __global__ __launch_bounds__(BLK) void k_state_bcast(const SelState *src, StateP
 #include "kth_rows_topp.hpp"
 #include "kth_rows_topp16.hpp"
 #include "kth_rows_sample.hpp"
+#include "kth_rows_sort.hpp"

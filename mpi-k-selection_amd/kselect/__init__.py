@@ -60,6 +60,7 @@ from ._lib import (  # noqa: F401
     KTH_PATH_WINDOW_FALLBACK,
     KTH_ROWS16_MAX_COLS,
     KTH_ROWS_MAX_COLS,
+    KTH_SORT_MAX_K,
     KTH_STATS_WORDS,
     KTH_TOPK_MAX_COLS,
     KTH_WIDE_MAX_COLS,
@@ -221,6 +222,32 @@ def _k16_values(bits, kind):
     if kind == KTH_K16_BF16:
         return (bits.astype(np.uint32) << np.uint32(16)).view(np.float32)
     return bits.view(_K16_NUMPY[kind])
+
+
+def _sort_kind(d_vals, d_idx, d_cnt, f32, kind):
+    """The dtype checks of sort_topk_rows.  Returns the call's flavour: "i32",
+    "f32" or a KTH_K16_* kind (kind given, or d_vals of a 16-bit dtype)."""
+    _need_i32(d_idx, "d_idx")
+    _need_i32(d_cnt, "d_cnt")
+    if f32:
+        _need_f32(d_vals, "d_vals")
+        return "f32"
+    name = str(getattr(d_vals, "dtype", "")).rsplit(".", 1)[-1]
+    if kind is not None or name in _K16_OF_DTYPE:
+        return _k16_kind(d_vals, kind, "d_vals")
+    _need_i32(d_vals, "d_vals")
+    return "i32"
+
+
+def _sorted_check(d_vals, k, d_cnt=None, need_cnt=False):
+    """sorted=True of the top-k wrappers: what the sort that follows cannot do
+    without, refused before anything is enqueued."""
+    if d_vals is None:
+        raise ValueError("sorted=True needs d_vals: the sort orders the values")
+    if int(k) > KTH_SORT_MAX_K:
+        raise ValueError(f"sorted=True needs k <= {KTH_SORT_MAX_K}, got {int(k)}")
+    if need_cnt and d_cnt is None:
+        raise ValueError("sorted=True needs d_cnt: the sort must know where each row's padding starts")
 
 
 def _stream_handle(stream):
@@ -415,13 +442,38 @@ class Selector:
         fn = LIB.kth_select_rows_f32 if f32 else LIB.kth_select_rows_i32
         check(fn(self._ctx, _ptr(d_keys), int(rows), int(cols), int(k), _ptr(d_out)), "kth_select_rows")
 
-    def topk_rows(self, d_keys, rows, cols, k, d_vals=None, d_idx=None, largest=False, f32=False):
+    def sort_topk_rows(self, d_vals, d_idx, rows, k, largest=False, f32=False, kind=None, d_cnt=None):
+        """Stable in-place sort of each row of a rows x k top-k output, best
+        first (kth_sort_topk_rows_*; asynchronous on the ctx stream): the first
+        clamp(d_cnt[r], 0, k) entries of row r (all k when d_cnt is None),
+        ascending in the order key, descending with largest=True; equal keys
+        keep their input order; the other entries are neither read nor written.
+        d_vals: int32, float32 with f32=True, or 16-bit elements (`kind` as
+        _k16_kind); d_idx: the int32 payload moved with the values, or None."""
+        flavour = _sort_kind(d_vals, d_idx, d_cnt, f32, kind)
+        head = (self._ctx, _ptr(d_vals), _ptr_or_none(d_idx), int(rows), int(k), _ptr_or_none(d_cnt),
+                1 if largest else 0)
+        if flavour == "f32":
+            check(LIB.kth_sort_topk_rows_f32(*head), "kth_sort_topk_rows_f32")
+        elif flavour == "i32":
+            check(LIB.kth_sort_topk_rows_i32(*head), "kth_sort_topk_rows_i32")
+        else:
+            check(LIB.kth_sort_topk_rows_k16(*head, flavour), "kth_sort_topk_rows_k16")
+
+    def topk_rows(self, d_keys, rows, cols, k, d_vals=None, d_idx=None, largest=False, f32=False, sorted=False):
         """Per row: the k smallest (largest=True: largest) keys and their columns,
-        in column order, ties broken by column (kth_topk_rows_*)."""
+        in column order, ties broken by column (kth_topk_rows_*).  sorted=True:
+        best first instead, ties still by column (sort_topk_rows on the same
+        stream; needs d_vals and k <= KTH_SORT_MAX_K)."""
+        if sorted:
+            _sorted_check(d_vals, k)
+            _sort_kind(d_vals, d_idx, None, f32, None)
         fn = LIB.kth_topk_rows_f32 if f32 else LIB.kth_topk_rows_i32
         check(fn(self._ctx, _ptr(d_keys), int(rows), int(cols), int(k), 1 if largest else 0,
                  _ptr(d_vals) if d_vals is not None else None, _ptr(d_idx) if d_idx is not None else None),
               "kth_topk_rows")
+        if sorted:
+            self.sort_topk_rows(d_vals, d_idx, rows, k, largest=largest, f32=f32)
 
     def rows16(self, d_keys, rows, cols, k, d_out, kind=None):
         """Per row of a rows x cols matrix of 16-bit device keys: the bits of the
@@ -433,20 +485,25 @@ class Selector:
         check(LIB.kth_select_rows_k16(self._ctx, _ptr(d_keys), int(rows), int(cols), int(k), kind, _ptr(d_out)),
               "kth_select_rows_k16")
 
-    def topk_rows16(self, d_keys, rows, cols, k, d_vals=None, d_idx=None, largest=False, kind=None):
+    def topk_rows16(self, d_keys, rows, cols, k, d_vals=None, d_idx=None, largest=False, kind=None, sorted=False):
         """Per row of 16-bit device keys: the k smallest (largest=True: largest)
         keys and their int32 columns, in column order, ties broken by column
         (kth_topk_rows_k16).  d_vals: rows x k 2-byte elements of the keys' kind
-        (a NaN canonical), d_idx: rows x k int32; either may be None, not both."""
+        (a NaN canonical), d_idx: rows x k int32; either may be None, not both.
+        sorted as in topk_rows."""
         kind = _k16_kind(d_keys, kind, "d_keys")
         if d_vals is not None:
             _k16_same_kind(d_keys, d_vals, kind, "d_vals")
         dt = getattr(d_idx, "dtype", None)
         if dt is not None and str(dt).rsplit(".", 1)[-1] != "int32":
             raise TypeError(f"d_idx must be int32, got {dt}")
+        if sorted:
+            _sorted_check(d_vals, k)
         check(LIB.kth_topk_rows_k16(self._ctx, _ptr(d_keys), int(rows), int(cols), int(k), 1 if largest else 0, kind,
                                     _ptr(d_vals) if d_vals is not None else None,
                                     _ptr(d_idx) if d_idx is not None else None), "kth_topk_rows_k16")
+        if sorted:
+            self.sort_topk_rows(d_vals, d_idx, rows, k, largest=largest, kind=kind)
 
     def rows_wide(self, d_keys, rows, cols, k, d_out, f32=False, ld=None):
         """Per row of a rows x cols matrix of int32 (f32=True: float32) device
@@ -461,22 +518,28 @@ class Selector:
         check(fn(self._ctx, _ptr(d_keys), int(rows), int(cols), int(cols if ld is None else ld), int(k), _ptr(d_out)),
               what)
 
-    def topk_rows_wide(self, d_keys, rows, cols, k, d_vals=None, d_idx=None, largest=False, f32=False, ld=None):
+    def topk_rows_wide(self, d_keys, rows, cols, k, d_vals=None, d_idx=None, largest=False, f32=False, ld=None,
+                       sorted=False):
         """Per row of such a matrix: the k smallest (largest=True: largest) keys
         and their int32 columns, in column order, ties broken by column
         (kth_topk_wide_rows_*).  d_vals: rows x k of the keys' type, d_idx: rows
-        x k int32; either may be None, not both."""
+        x k int32; either may be None, not both.  sorted as in topk_rows."""
         if f32:
             _need_f32(d_keys, "d_keys")
             _need_f32(d_vals, "d_vals")
         dt = getattr(d_idx, "dtype", None)
         if dt is not None and str(dt).rsplit(".", 1)[-1] != "int32":
             raise TypeError(f"d_idx must be int32, got {dt}")
+        if sorted:
+            _sorted_check(d_vals, k)
+            _sort_kind(d_vals, d_idx, None, f32, None)
         fn, what = ((LIB.kth_topk_wide_rows_f32, "kth_topk_wide_rows_f32") if f32 else
                     (LIB.kth_topk_wide_rows_i32, "kth_topk_wide_rows_i32"))
         check(fn(self._ctx, _ptr(d_keys), int(rows), int(cols), int(cols if ld is None else ld), int(k),
                  1 if largest else 0, _ptr(d_vals) if d_vals is not None else None,
                  _ptr(d_idx) if d_idx is not None else None), what)
+        if sorted:
+            self.sort_topk_rows(d_vals, d_idx, rows, k, largest=largest, f32=f32)
 
     def rows_wide16(self, d_keys, rows, cols, k, d_out, kind=None, ld=None):
         """rows16 for rows of up to KTH_WIDE_MAX_COLS columns: per row of 16-bit
@@ -489,21 +552,27 @@ class Selector:
                                            int(cols if ld is None else ld), int(k), kind, _ptr(d_out)),
               "kth_select_wide_rows_k16")
 
-    def topk_rows_wide16(self, d_keys, rows, cols, k, d_vals=None, d_idx=None, largest=False, kind=None, ld=None):
+    def topk_rows_wide16(self, d_keys, rows, cols, k, d_vals=None, d_idx=None, largest=False, kind=None, ld=None,
+                         sorted=False):
         """topk_rows16 for such rows: the k smallest (largest=True: largest) keys
         and their int32 columns, in column order, ties broken by column
         (kth_topk_wide_rows_k16).  d_vals: rows x k 2-byte elements of the keys'
-        kind (a NaN canonical), d_idx: rows x k int32; either may be None."""
+        kind (a NaN canonical), d_idx: rows x k int32; either may be None.
+        sorted as in topk_rows."""
         kind = _k16_kind(d_keys, kind, "d_keys")
         if d_vals is not None:
             _k16_same_kind(d_keys, d_vals, kind, "d_vals")
         dt = getattr(d_idx, "dtype", None)
         if dt is not None and str(dt).rsplit(".", 1)[-1] != "int32":
             raise TypeError(f"d_idx must be int32, got {dt}")
+        if sorted:
+            _sorted_check(d_vals, k)
         check(LIB.kth_topk_wide_rows_k16(self._ctx, _ptr(d_keys), int(rows), int(cols), int(cols if ld is None else ld),
                                          int(k), 1 if largest else 0, kind,
                                          _ptr(d_vals) if d_vals is not None else None,
                                          _ptr(d_idx) if d_idx is not None else None), "kth_topk_wide_rows_k16")
+        if sorted:
+            self.sort_topk_rows(d_vals, d_idx, rows, k, largest=largest, kind=kind)
 
     def rows_wide_var(self, d_keys, rows, cols, k, d_out, f32=False, d_lens=None, d_ks=None, ld=None):
         """rows_wide with a length and a rank per row, read on the device when
@@ -522,13 +591,14 @@ class Selector:
                  _ptr_or_none(d_ks), int(k), _ptr(d_out)), what)
 
     def topk_rows_wide_var(self, d_keys, rows, cols, k, d_vals=None, d_idx=None, largest=False, f32=False,
-                           d_lens=None, d_ks=None, d_cnt=None, ld=None):
+                           d_lens=None, d_ks=None, d_cnt=None, ld=None, sorted=False):
         """topk_rows_wide with a length and a k per row, read on the device when
         the launches run (kth_topk_wide_rows_var_*).  k is the output stride and
         the bound of every row's k_r = min(clamp(d_ks[r], 0, k), len_r); entries
         [k_r, k) of a row are written as padding (index -1, the zero word) and
         d_cnt[r] = k_r.  d_lens, d_ks, d_cnt: `rows` int32 device elements, each
-        may be None."""
+        may be None.  sorted=True: the k_r entries best first, the padding left
+        where it is (sort_topk_rows with this d_cnt, which it then needs)."""
         if f32:
             _need_f32(d_keys, "d_keys")
             _need_f32(d_vals, "d_vals")
@@ -536,11 +606,16 @@ class Selector:
         _need_i32(d_lens, "d_lens")
         _need_i32(d_ks, "d_ks")
         _need_i32(d_cnt, "d_cnt")
+        if sorted:
+            _sorted_check(d_vals, k, d_cnt, need_cnt=True)
+            _sort_kind(d_vals, d_idx, d_cnt, f32, None)
         fn, what = ((LIB.kth_topk_wide_rows_var_f32, "kth_topk_wide_rows_var_f32") if f32 else
                     (LIB.kth_topk_wide_rows_var_i32, "kth_topk_wide_rows_var_i32"))
         check(fn(self._ctx, _ptr(d_keys), int(rows), int(cols), int(cols if ld is None else ld), _ptr_or_none(d_lens),
                  _ptr_or_none(d_ks), int(k), 1 if largest else 0, _ptr_or_none(d_vals), _ptr_or_none(d_idx),
                  _ptr_or_none(d_cnt)), what)
+        if sorted:
+            self.sort_topk_rows(d_vals, d_idx, rows, k, largest=largest, f32=f32, d_cnt=d_cnt)
 
     def rows_wide16_var(self, d_keys, rows, cols, k, d_out, kind=None, d_lens=None, d_ks=None, ld=None):
         """rows_wide_var for rows of 16-bit keys (kth_select_wide_rows_var_k16)."""
@@ -554,7 +629,7 @@ class Selector:
               "kth_select_wide_rows_var_k16")
 
     def topk_rows_wide16_var(self, d_keys, rows, cols, k, d_vals=None, d_idx=None, largest=False, kind=None,
-                             d_lens=None, d_ks=None, d_cnt=None, ld=None):
+                             d_lens=None, d_ks=None, d_cnt=None, ld=None, sorted=False):
         """topk_rows_wide_var for rows of 16-bit keys (kth_topk_wide_rows_var_k16)."""
         kind = _k16_kind(d_keys, kind, "d_keys")
         if d_vals is not None:
@@ -563,10 +638,14 @@ class Selector:
         _need_i32(d_lens, "d_lens")
         _need_i32(d_ks, "d_ks")
         _need_i32(d_cnt, "d_cnt")
+        if sorted:
+            _sorted_check(d_vals, k, d_cnt, need_cnt=True)
         check(LIB.kth_topk_wide_rows_var_k16(self._ctx, _ptr(d_keys), int(rows), int(cols),
                                              int(cols if ld is None else ld), _ptr_or_none(d_lens), _ptr_or_none(d_ks),
                                              int(k), 1 if largest else 0, kind, _ptr_or_none(d_vals),
                                              _ptr_or_none(d_idx), _ptr_or_none(d_cnt)), "kth_topk_wide_rows_var_k16")
+        if sorted:
+            self.sort_topk_rows(d_vals, d_idx, rows, k, largest=largest, kind=kind, d_cnt=d_cnt)
 
     def nucleus_rows_wide(self, d_keys, rows, cols, d_n=None, d_thr=None, p=1.0, temp=1.0, d_lens=None, d_ps=None,
                           d_temps=None, ld=None):
@@ -603,11 +682,12 @@ class Selector:
                                             _ptr_or_none(d_thr)), "kth_nucleus_wide_rows_k16")
 
     def topp_rows_wide(self, d_keys, rows, cols, k, d_vals=None, d_idx=None, p=1.0, temp=1.0, d_lens=None, d_ks=None,
-                       d_ps=None, d_temps=None, d_cnt=None, ld=None):
+                       d_ps=None, d_temps=None, d_cnt=None, ld=None, sorted=False):
         """Top-k cap and top-p nucleus of every float32 row in one call
         (kth_topp_wide_rows_f32): the outputs of topk_rows_wide_var(largest=True)
         with each row's rank min(n_r, clamp(d_ks[r], 0, k)), n_r the nucleus size
-        of nucleus_rows_wide.  k is the output stride."""
+        of nucleus_rows_wide.  k is the output stride.  sorted=True: each row's
+        kept entries largest first (as topk_rows_wide_var; needs d_cnt)."""
         _need_f32(d_keys, "d_keys")
         _need_f32(d_vals, "d_vals")
         _need_i32(d_idx, "d_idx")
@@ -616,13 +696,17 @@ class Selector:
         _need_i32(d_cnt, "d_cnt")
         _need_f32(d_ps, "d_ps")
         _need_f32(d_temps, "d_temps")
+        if sorted:
+            _sorted_check(d_vals, k, d_cnt, need_cnt=True)
         check(LIB.kth_topp_wide_rows_f32(self._ctx, _ptr(d_keys), int(rows), int(cols), int(cols if ld is None else ld),
                                          _ptr_or_none(d_lens), _ptr_or_none(d_ks), int(k), _ptr_or_none(d_ps), float(p),
                                          _ptr_or_none(d_temps), float(temp), _ptr_or_none(d_vals), _ptr_or_none(d_idx),
                                          _ptr_or_none(d_cnt)), "kth_topp_wide_rows_f32")
+        if sorted:
+            self.sort_topk_rows(d_vals, d_idx, rows, k, largest=True, f32=True, d_cnt=d_cnt)
 
     def topp_rows_wide16(self, d_keys, rows, cols, k, d_vals=None, d_idx=None, p=1.0, temp=1.0, kind=None, d_lens=None,
-                         d_ks=None, d_ps=None, d_temps=None, d_cnt=None, ld=None):
+                         d_ks=None, d_ps=None, d_temps=None, d_cnt=None, ld=None, sorted=False):
         """topp_rows_wide for float16 / bfloat16 rows (kth_topp_wide_rows_k16)."""
         kind = _k16_kind(d_keys, kind, "d_keys")
         if d_vals is not None:
@@ -633,10 +717,14 @@ class Selector:
         _need_i32(d_cnt, "d_cnt")
         _need_f32(d_ps, "d_ps")
         _need_f32(d_temps, "d_temps")
+        if sorted:
+            _sorted_check(d_vals, k, d_cnt, need_cnt=True)
         check(LIB.kth_topp_wide_rows_k16(self._ctx, _ptr(d_keys), int(rows), int(cols), int(cols if ld is None else ld),
                                          _ptr_or_none(d_lens), _ptr_or_none(d_ks), int(k), _ptr_or_none(d_ps), float(p),
                                          _ptr_or_none(d_temps), float(temp), kind, _ptr_or_none(d_vals),
                                          _ptr_or_none(d_idx), _ptr_or_none(d_cnt)), "kth_topp_wide_rows_k16")
+        if sorted:
+            self.sort_topk_rows(d_vals, d_idx, rows, k, largest=True, kind=kind, d_cnt=d_cnt)
 
     def reserve_topp_rows(self, rows, cols):
         """Pre-size the scratch of the top-p calls, the var top-k's included

@@ -30,6 +30,7 @@ KTH_TOPK_MAX_COLS = 4096
 KTH_ROWS16_MAX_COLS = 8192
 KTH_WIDE_MAX_COLS = 1 << 24
 KTH_WIDE_MAX_SLICES = 256
+KTH_SORT_MAX_K = 4096
 KTH_MULTI_MAX_RANKS = 8
 # kth_ctx_test_hook (tests only): fault injectors, off in every new ctx
 KTH_HOOK_FAULT_TOPK_RANK, KTH_HOOK_FAULT_BARRIER, KTH_HOOK_TOPK_SEG_CAP = 1, 2, 3
@@ -187,6 +188,11 @@ PROTOS = {
                                                 ctypes.c_int32, c_vp, ctypes.c_float, c_vp, ctypes.c_float, c_vp,
                                                 ctypes.c_int, c_vp, c_vp]),
     "kth_ctx_reserve_sample_rows": (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int32]),
+    # sorted top-k rows: ctx, d_vals, d_idx, rows, k, d_cnt, largest, [kind]
+    "kth_sort_topk_rows_i32": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int64, ctypes.c_int32, c_vp, ctypes.c_int]),
+    "kth_sort_topk_rows_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int64, ctypes.c_int32, c_vp, ctypes.c_int]),
+    "kth_sort_topk_rows_k16": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int64, ctypes.c_int32, c_vp, ctypes.c_int,
+                                              ctypes.c_int]),
     "kth_topk_i32": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, c_vp, c_vp]),
     "kth_topk_f32": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, c_vp, c_vp]),
     "kth_topk_k16": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
